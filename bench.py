@@ -1,6 +1,7 @@
 """Benchmark: swapped 256x256 frames/s of GHOST's swap forward on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N --steps K --warmup W --batch 64 --backbone unet --num-blocks 2 --identities 1]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (driver's multi-GPU form)
 
 Headline (BASELINE config 2 at N = 1, config 4 at N > 1): one step = one faceshifter_batch of B
@@ -11,7 +12,11 @@ value = N*B*K / max-over-ranks wall time of the K timed steps.  ``--identities 4
 --num-blocks 3`` makes the headline BASELINE config 5 (mixed-identity batches, per-sample identity
 rows).
 
-Besides the JSON line's throughput, rank 0 at N = 1 reports
+A plain run does only that: set up, W warm-up steps, the K timed steps, one JSON line (value, ms_per_step).
+``--dump-outputs DIR`` also writes the last timed step's result, the swapped uint8 frames of every rank in rank
+order, to DIR/swapped.npy (float32; the inputs are seeded, so two builds can be compared frame for frame).
+
+With ``--full``, besides the JSON line's throughput, rank 0 at N = 1 reports
 * roofline: the dominant AAD kernel, aad_v5_kernel<__bf16,64,2,true,2,true> (the two AADLayers of AADBlk8
   that read the same h_in / z_attr at 256x256, h_in sampled through the bilinear x2 upsample of AADBlk7's
   128x128 output; one of them writes the 3x3 RGB conv's tap partials), HBM-bound.  ``achieved`` = the bytes
@@ -84,7 +89,32 @@ def parse(argv=None):
     # the launcher's CPU rehearsal (tests/test_dp_cpu.py): gloo ranks on the CPU with a stand-in swap, the same
     # timed region / record / relay as the GPU run
     ap.add_argument("--standin-cpu", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the per-kernel profile / roofline figures, the side legs (--legs) and "
+                         "the CPU baseline (--cpu-batches); without it a run sets up, warms up, times the steps and "
+                         "prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (the swapped uint8 frames of "
+                         "every rank, in rank order) to DIR/swapped.npy as float32")
+    a = ap.parse_args(argv)
+    if not a.full:
+        a.legs, a.cpu_batches, a.no_profile = "", "", True
+    return a
+
+
+DUMP_BYTES = 64 * 1000 * 1000     # --dump-outputs writes at most this much
+
+
+def dump_outputs(path, frames: torch.Tensor) -> None:
+    """Write the last timed step's result (N x 256 x 256 x 3 uint8 swaps) to path/swapped.npy as float32; of an
+    output above DUMP_BYTES a fixed, seeded choice of whole frames (in ascending frame order)."""
+    os.makedirs(path, exist_ok=True)
+    n = frames.shape[0]
+    keep = max(1, DUMP_BYTES // (4 * frames[0].numel()))
+    if n > keep:
+        rows = np.sort(np.random.Generator(np.random.PCG64(2024)).choice(n, size=keep, replace=False))
+        frames = frames.index_select(0, torch.from_numpy(rows).to(frames.device))
+    np.save(os.path.join(path, "swapped.npy"), frames.cpu().numpy().astype(np.float32))
 
 
 _MANGLED_TYPES = {"__bf16": "DF16b", "_Float16": "DF16_", "float": "f"}
@@ -855,7 +885,13 @@ def standin_main(a, world, rank):
     pipe = GatherPipeline(swap, (B, 4, 4, 3), dev, depth=2)
     crops = torch.full((B, 4, 4, 3), rank, dtype=torch.uint8)
     per = []
-    el = timed_region(lambda: pipe.submit(crops), pipe.drain, a.steps, a.warmup, world, dev, per_rank=per)
+    last = [None]
+
+    def step():
+        last[0] = pipe.submit(crops)
+    el = timed_region(step, pipe.drain, a.steps, a.warmup, world, dev, per_rank=per)
+    if a.dump_outputs and rank == 0 and last[0] is not None:
+        dump_outputs(a.dump_outputs, pipe.result(last[0]))
     if rank == 0:
         res = headline_record(world, B, a.steps, a.warmup, el, a.backbone, a.num_blocks, a.identities, a.dtype, 1, per)
         res["data"] = "synthetic (CPU stand-in swap, gloo)"
@@ -915,8 +951,10 @@ def main(argv=None):
                           depth=2 if os.environ.get("GHOST_DP_OVERLAP", "1") != "0" else 1,
                           streams=max(1, a.streams))
 
+    last = [None]
+
     def step():
-        slot = pipe.submit(crops)
+        slot = last[0] = pipe.submit(crops)
         if pipe.depth == 1:
             pipe.result(slot)
 
@@ -933,6 +971,8 @@ def main(argv=None):
 
     per_rank = []
     el = timed_region(step, pipe.drain, a.steps, a.warmup, world, dev, before_timed, per_rank)
+    if a.dump_outputs and rank == 0 and last[0] is not None:
+        dump_outputs(a.dump_outputs, pipe.result(last[0]))
     iso = {}
     clock = {"timed": (0.0, 0), "isolated": (0.0, 0)}
     if prof:

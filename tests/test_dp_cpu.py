@@ -601,3 +601,41 @@ def test_bench_single_process_default_is_one_rank_cpu():
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     assert rec["n_gpus"] == 1 and rec["rccl_world"] == 1 and len(rec["per_rank_s"]) == 1
+
+
+def test_bench_dump_outputs_and_plain_run_cpu(tmp_path, monkeypatch):
+    """``--dump-outputs DIR`` writes what the last timed step returned (here the stand-in's 255 - crop, channels
+    flipped, of rank 0's all-zero crops) as float32 DIR/swapped.npy, the same from run to run; a plain run stops at
+    the headline (no legs, CPU baseline or per-kernel profile), ``--full`` restores the defaults; an output above
+    bench.DUMP_BYTES is cut to a fixed choice of whole frames."""
+    import json
+    import subprocess
+
+    import bench
+    dumps = []
+    for d in ("a", "b"):
+        r = subprocess.run(_bench_cmd("--standin-cpu", "--steps", "2", "--warmup", "1", "--batch", "3",
+                                      "--dump-outputs", str(tmp_path / d)),
+                           capture_output=True, text=True, env=_clean_env(), timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = json.loads(r.stdout.strip().splitlines()[-1])
+        assert rec["steps"] == 2 and rec["ms_per_step"] >= 0 and "legs" not in rec and "cpu_baseline" not in rec
+        assert [p.name for p in (tmp_path / d).iterdir()] == ["swapped.npy"]
+        dumps.append(np.load(tmp_path / d / "swapped.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (3, 4, 4, 3)
+    assert (dumps[0] == 255.0).all() and np.array_equal(dumps[0], dumps[1])
+
+    plain, full = bench.parse([]), bench.parse(["--full"])
+    assert (plain.legs, plain.cpu_batches, plain.no_profile) == ("", "", True)
+    assert "d2h" in full.legs and full.cpu_batches == "1,64" and not full.no_profile
+    assert bench.parse(["--full", "--legs", "", "--no-profile"]).legs == ""
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 4 * 4 * 3 * 4)      # room for 3 float32 frames of 4 x 4 x 3
+    frames = torch.arange(10, dtype=torch.uint8).reshape(10, 1, 1, 1).expand(10, 4, 4, 3)
+    bench.dump_outputs(str(tmp_path / "c"), frames)
+    bench.dump_outputs(str(tmp_path / "d"), frames)
+    c = np.load(tmp_path / "c" / "swapped.npy")
+    assert c.shape == (3, 4, 4, 3) and c.dtype == np.float32 and c.nbytes <= bench.DUMP_BYTES
+    rows = c[:, 0, 0, 0]
+    assert (np.diff(rows) > 0).all() and (c == rows[:, None, None, None]).all()
+    assert np.array_equal(c, np.load(tmp_path / "d" / "swapped.npy"))

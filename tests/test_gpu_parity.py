@@ -19,7 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from oracle import aei_ref
+from oracle import aei_ref, golden_io
 
 pytestmark = pytest.mark.gpu
 
@@ -28,7 +28,7 @@ DEV = torch.device("cuda:0")
 
 
 def gold(name):
-    return np.load(os.path.join(GOLD, name + ".npz"))
+    return golden_io.load(GOLD, name)
 
 
 @pytest.fixture(scope="module")

@@ -6,14 +6,14 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import aei_ref
+from oracle import aei_ref, golden_io
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = ["aei_unet2_b2", "aei_linknet3_b2", "aei_unet1_b1", "aei_unet3_b1", "aei_resnet2_b1"]
 
 
 def _load(name):
-    return np.load(os.path.join(GOLD, name + ".npz"))
+    return golden_io.load(GOLD, name)
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -7,8 +7,8 @@
 #   tests          pytest -m gpu (one process, per-test timeout)          -> gpurun_out/gputests.log
 #   tests:EXPR     the same, -k EXPR                                       -> gpurun_out/gputests.log
 #   smoke          __graft_entry__.smoke()                                 -> gpurun_out/smoke.log
-#   bench          python bench.py (default legs + CPU baseline)           -> gpurun_out/bench.log
-#   quick          bench.py without legs / CPU baseline                    -> gpurun_out/quick.log
+#   bench          python bench.py --full (default legs + CPU baseline)    -> $OUT/bench.log (OUT=${GHOST_OUT:-out})
+#   quick          bench.py --full without legs / CPU baseline (headline + roofline) -> quick.log, beside the other logs
 #   quick1         the same with one batch in flight (--streams 1)         -> gpurun_out/quick1.log
 #   trace          one-stream kernel trace, per-step kernel sequence       -> gpurun_out/step_trace.txt
 #   trace1         the same at B = 1                                       -> gpurun_out/step_trace_b1.txt
@@ -33,6 +33,9 @@
 export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 mkdir -p gpurun_out
 Q='--legs "" --cpu-batches ""'
+# every bench.py step here reads the roofline / legs part of the line, which a plain run no longer has
+BENCH_ARGS="--full $BENCH_ARGS"
+OUT=${GHOST_OUT:-out}
 ok() { rc=$1; [ $rc -eq 0 ] || [ $rc -eq 1 ] || { echo "[gpu.sh] stop: rc=$rc"; exit $rc; }; }
 must() { rc=$1; [ $rc -eq 0 ] || { echo "[gpu.sh] stop: rc=$rc"; exit $rc; }; }
 last() { python3 -c "import json,sys;d=json.loads(open('$1').read().strip().split('\n')[-1]);r=d.get('roofline',{});print(sys.argv[1],d['value'],d['ms_per_step'],'live',r.get('live_clock_us'),'iso',r.get('isolated',{}).get('avg_launch_us'))" "$2"; }
@@ -42,7 +45,7 @@ for step in "$@"; do
     tests) timeout -k 10 900 python -u -m pytest tests -m gpu -v --maxfail 6 --timeout 150 --timeout-method thread > gpurun_out/gputests.log 2>&1; ok $? ;;
     tests:*) timeout -k 10 600 python -u -m pytest tests -m gpu -v --timeout 150 --timeout-method thread -k "${step#tests:}" > gpurun_out/gputests.log 2>&1; ok $? ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; must $? ;;
-    bench) timeout -k 10 600 python -u bench.py > gpurun_out/bench.log 2>&1; must $? ;;
+    bench) mkdir -p "$OUT" && timeout -k 10 600 python -u bench.py --full > "$OUT/bench.log" 2>&1; must $? ;;
     quick) eval timeout -k 10 300 python -u bench.py $Q $BENCH_ARGS > gpurun_out/quick.log 2>&1; must $? ;;
     quick1) eval timeout -k 10 300 python -u bench.py $Q --streams 1 $BENCH_ARGS > gpurun_out/quick1.log 2>&1; must $? ;;
     trace1)
