@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cv_warp.h"
 #include "ghost_amd.h"
 #include "ghost_common.h"
 
@@ -23,34 +24,6 @@ int set_last_error(int rc, const char* msg);
 }
 
 namespace {
-
-// One rounding per operation, never fused: HIP's __fmul_rn / __dadd_rn ... are plain operators compiled with the
-// translation unit's contraction mode, so after inlining the compiler fuses a*b + c into an FMA.  These carry no
-// contract flag (the pragma applies to the operations written in their bodies).
-__device__ __forceinline__ float f_mul(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float f_add(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float f_sub(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
-__device__ __forceinline__ double d_mul(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ double d_add(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ double d_sub(double a, double b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
 
 struct BlendArgs {
   uint8_t* frames; long fstride; int H, W;
@@ -101,24 +74,6 @@ __global__ void __launch_bounds__(256) blend_kernel(const BlendArgs a) {
 // weights, fx = (float)((d + 0.5) * scale - 0.5), clamped at the borders; horizontal pass in int, vertical
 // pass as the vector VResizeLinear: (((D0 >> 4) * b0 >> 16) + ((D1 >> 4) * b1 >> 16) + 2) >> 2.  Integer
 // arithmetic throughout: bit-exact against oracle/blend_ref.resize_linear_u8.
-struct RzTap {
-  int s0, s1, w0, w1;
-};
-__device__ RzTap rz_tap(int d, int src_n, int dst_n) {
-  const double scale = 1.0 / ((double)dst_n / (double)src_n);
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  int s0 = (int)floorf(f);
-  f = f_sub(f, (float)s0);
-  if (s0 < 0) { f = 0.f; s0 = 0; }
-  if (s0 >= src_n - 1) { f = 0.f; s0 = src_n - 1; }
-  RzTap t;
-  t.s0 = s0;
-  t.s1 = min(s0 + 1, src_n - 1);
-  t.w0 = (int)rintf(f_mul(f_sub(1.f, f), 2048.f));
-  t.w1 = (int)rintf(f_mul(f, 2048.f));
-  return t;
-}
-
 __global__ void __launch_bounds__(256) resize_u8_linear_kernel(const uint8_t* __restrict__ src, long sstride, int Hs,
                                                                int Ws, uint8_t* __restrict__ dst, long dstride, int Hd,
                                                                int Wd) {
@@ -149,24 +104,6 @@ __global__ void __launch_bounds__(256) resize_u8_linear_kernel(const uint8_t* __
 // the map A (the double inverse of the given matrix, host-side) sampled at X = (rint((A1 y + A2) 1024) + 16 +
 // rint(A0 x 1024)) >> 5: pixel X >> 5, sub-pixel X & 31; bilinear weights from the 32 x 32 grid (15-bit integers
 // for uint8 with (sum + 2^14) >> 15, floats for the mask).
-struct CvWarp {
-  int sx, sy;            // top-left source pixel
-  float wx1, wy1;        // sub-pixel weights (multiples of 1/32)
-};
-__device__ CvWarp cv_warp_pos(const double* A, int x, int y) {
-  const long adelta = __double2ll_rn(d_mul(d_mul(A[0], (double)x), 1024.0));
-  const long bdelta = __double2ll_rn(d_mul(d_mul(A[3], (double)x), 1024.0));
-  const long X0 = __double2ll_rn(d_mul(d_add(d_mul(A[1], (double)y), A[2]), 1024.0)) + 16;
-  const long Y0 = __double2ll_rn(d_mul(d_add(d_mul(A[4], (double)y), A[5]), 1024.0)) + 16;
-  const long X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-  CvWarp w;
-  w.sx = (int)(X >> 5);
-  w.sy = (int)(Y >> 5);
-  w.wx1 = (float)(X & 31) * (1.f / 32.f);
-  w.wy1 = (float)(Y & 31) * (1.f / 32.f);
-  return w;
-}
-
 struct ImageBlendArgs {
   uint8_t* frame; int H, W;
   const uint8_t* swaps; long sstride;   // [J][224][224][3]

@@ -1,8 +1,8 @@
 """Per-identity swap loop of model_inference (utils/inference/core.py:13-26, :57-88).
 
 Only the per-frame part is here: crops in, swapped crops out with the reference's
-``present`` bookkeeping (frames without a face yield ``[]``).  Detection, alignment and
-landmarks stay on the host pipeline of the reference (out of scope).
+``present`` bookkeeping (frames without a face yield ``[]``).  Detection and landmarks stay on
+the host pipeline of the reference (out of scope); alignment from the detector's keypoints is ``align.py``.
 
 * ``resize_frames`` — video_processing.py:174-188 on the device: the 224x224 aligned crops of one identity
   (``[]`` where no face was found) -> ``present`` and the 256x256 crops, resized by the cv2 INTER_LINEAR

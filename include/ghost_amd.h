@@ -24,6 +24,8 @@
  *   network/AADLayer.py:64,71    Conv2d 3x3 of AAD_ResBlk (+ residual)     -> ghost_conv2d_nhwc
  *   network/AADLayer.py:16,24    InstanceNorm2d statistics                 -> ghost_instnorm_stats_nhwc
  *   network/AEI_Net.py:94,125    F.interpolate(x2, bilinear, align_corners) -> ghost_upsample2x_nhwc
+ *   utils/inference/video_processing.py:134,163,184 + utils/inference/image_processing.py:18-19
+ *                                cv2.warpAffine(frame, M, (224, 224)) + cv2.resize(crop, (256, 256)) -> ghost_align_crops_u8
  *
  * Activations crossing this ABI are NHWC with an explicit channel stride `ld`
  * (elements between consecutive pixels).  Packed weight layouts are documented
@@ -298,6 +300,22 @@ int ghost_resize_u8_linear(const uint8_t* src, int64_t src_stride, int F, int Hs
  * OpenCV does: ghost_amd.inference.blend.cv_warp_map). */
 int ghost_blend_image_u8(uint8_t* frame, int H, int W, const uint8_t* swaps, int64_t swap_stride, int J, int S,
                          const double* masks, int64_t mask_stride, const double* maps, void* stream);
+
+/* ---- aligned crops from device-resident frames ----
+ * utils/inference/image_processing.py:18-19 (crop_face) and utils/inference/video_processing.py:134,163
+ * (crop_frames_and_get_transforms): cv2.warpAffine(frame, M, (S, S), borderValue=0.0) per face, and
+ * video_processing.py:184 (resize_frames): cv2.resize(crop, (R, R)), from the uint8 frames [F,H,W,3] that
+ * ghost_blend_swaps_u8 later composites into.  For crop n: crops[n] = warpAffine(frames[frame_index[n]], M_n, (S, S))
+ * INTER_LINEAR, constant 0 border, in OpenCV's fixed point; maps[n] = the [2][3] double matrix warpAffine samples
+ * with, cv2.invertAffineTransform(M_n) computed on the host in double; resized[n] = cv2.resize(crops[n], (R, R))
+ * INTER_LINEAR as ghost_resize_u8_linear computes it, made in the same launch from the tile held in LDS.
+ * frame_index, maps and valid are device arrays of N; valid may be NULL, valid[n] == 0 leaves row n of both outputs
+ * untouched, and so does a frame_index[n] outside [0, F).  crops or resized may be NULL, not both.  The fused resize
+ * covers S % 7 == 0 with R == S / 7 * 8 (224 -> 256); any other (S, R) with resized != NULL is GHOST_EINVAL: crop
+ * with resized = NULL and call ghost_resize_u8_linear.  N <= 65535; N == 0 returns GHOST_OK without a launch. */
+int ghost_align_crops_u8(const uint8_t* frames, int64_t frame_stride, int F, int H, int W, const int32_t* frame_index,
+                         const double* maps, const int32_t* valid, int N, int S, uint8_t* crops, int64_t crop_stride,
+                         uint8_t* resized, int64_t resized_stride, int R, void* stream);
 
 /* ---- face masks (face_mask_static, utils/inference/masks.py:38-107) ----
  * Host, CPU only (no device pointers): for F frames of 106 float32 landmarks [F][106][2] and their
