@@ -68,6 +68,9 @@ _SIGS = {
     "ghost_resize_u8_linear": (i32, [vp, i64, i32, i32, i32, vp, i64, i32, i32, vp]),
     "ghost_blend_image_u8": (i32, [vp, i32, i32, vp, i64, i32, i32, vp, i64, vp, vp]),
     "ghost_align_crops_u8": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, i32, i32, vp, i64, vp, i64, i32, vp]),
+    "ghost_roi_copy_u8": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, i32, i32, vp]),
+    "ghost_align_crops_roi_u8": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i64, vp, i64, i32, vp]),
+    "ghost_blend_swaps_roi_u8": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, vp, i64, i32, i32, vp, i64, vp, vp, vp]),
     "ghost_mask_polygons": (i32, [vp, i32, i32, vp, vp, vp]),
     "ghost_face_masks_workspace_bytes": (i64, [i32, i32, i32]),
     "ghost_face_masks": (i32, [vp, vp, vp, i32, i32, i32, vp, i64, vp, i64, vp]),

@@ -6,14 +6,12 @@
 // fixed point (cv_warp.h): bit-exact against oracle/blend_ref.warp_affine_cv(..., "constant") and
 // resize_linear_u8 of it.
 //
-// One launch makes both outputs.  A workgroup owns a 28 x 28 tile of the S x S crop: it gathers the tile (plus a
-// one-pixel halo when a resize follows) from the frame into LDS, stores it, and resizes out of LDS.  For R = 8 S / 7
-// output rows [8k, 8k+8) read crop rows [7k-1, 7k+7] (clamped at the image edges), so the 30 x 30 LDS tile yields a
-// 32 x 32 output tile and the crop never makes a round trip through memory.  OpenCV's per-column (adelta, bdelta)
-// and per-row (X0, Y0) terms and the resize taps are tables per tile; the per-pixel work is integer.
+// One launch makes both outputs: a workgroup owns a 28 x 28 tile of the S x S crop (align_tile.h, which the ROI path's
+// ghost_align_crops_roi_u8 shares); here a tap is a pixel of a whole frame.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "align_tile.h"
 #include "cv_warp.h"
 #include "ghost_amd.h"
 #include "ghost_common.h"
@@ -24,153 +22,29 @@ int set_last_error(int rc, const char* msg);
 
 namespace {
 
-constexpr int kTile = 28;              // crop pixels per tile side
-constexpr int kSide = kTile + 2;       // with the halo
-constexpr int kOut = 32;               // resized pixels per tile side (kTile * 8 / 7)
-// LDS row: tile column c in [-1, 28] at byte 4 + 3c, so the interior starts dword-aligned
-constexpr int kRow = 92;
-
 struct AlignArgs {
   const uint8_t* frames; int64_t fstride; int F, H, W;
   const int32_t* frame_index;
   const double* maps;
   const int32_t* valid;
-  int S;
-  uint8_t* crops; int64_t cstride;
-  uint8_t* resized; int64_t rstride; int R;
-  int tiles;                           // per side
+  AlignOut out;
 };
 
-struct LocalTap {
-  int o0, o1, w0, w1;                  // LDS offsets of the two taps (bytes for columns, rows for rows), weights
+struct FrameSource {
+  const uint8_t* base; int H, W;
+  __device__ __forceinline__ const uint8_t* tap(long tx, long ty) const {
+    if (tx < 0 || tx >= W || ty < 0 || ty >= H) return nullptr;
+    return base + (ty * (int64_t)W + tx) * 3;
+  }
 };
 
 __global__ void __launch_bounds__(256) align_crops_kernel(const AlignArgs a) {
-  __shared__ __align__(16) uint8_t tile[kSide * kRow];
-  __shared__ long colA[kSide], colB[kSide], rowX[kSide], rowY[kSide];
-  __shared__ LocalTap rzc[kOut], rzr[kOut];
-
   const int n = blockIdx.y;
   if (a.valid && !a.valid[n]) return;
   const int fi = a.frame_index[n];
   if (fi < 0 || fi >= a.F) return;     // never read through a bad index
-  const int tid = threadIdx.x;
-  const int tyi = blockIdx.x / a.tiles, txi = blockIdx.x - tyi * a.tiles;
-  const int ox = txi * kTile, oy = tyi * kTile;          // crop coordinates of the tile's interior
-  const int S = a.S;
-  const int halo = a.resized ? 1 : 0;
-  const double* A = a.maps + (int64_t)n * 6;
-
-  // ---- tables (one wave each) ----
-  if (tid < kSide) {
-    cv_warp_col(A, ox + tid - 1, &colA[tid], &colB[tid]);
-  } else if (tid >= 64 && tid < 64 + kSide) {
-    cv_warp_row(A, oy + tid - 64 - 1, &rowX[tid - 64], &rowY[tid - 64]);
-  } else if (a.resized && tid >= 128 && tid < 128 + kOut) {
-    const int d = min(txi * kOut + tid - 128, a.R - 1);
-    const RzTap t = rz_tap(d, S, a.R);
-    LocalTap l;
-    l.o0 = 4 + 3 * min(max(t.s0 - ox, -1), kTile);
-    l.o1 = 4 + 3 * min(max(t.s1 - ox, -1), kTile);
-    l.w0 = t.w0;
-    l.w1 = t.w1;
-    rzc[tid - 128] = l;
-  } else if (a.resized && tid >= 192 && tid < 192 + kOut) {
-    const int d = min(tyi * kOut + tid - 192, a.R - 1);
-    const RzTap t = rz_tap(d, S, a.R);
-    LocalTap l;
-    l.o0 = (min(max(t.s0 - oy, -1), kTile) + 1) * kRow;
-    l.o1 = (min(max(t.s1 - oy, -1), kTile) + 1) * kRow;
-    l.w0 = t.w0;
-    l.w1 = t.w1;
-    rzr[tid - 192] = l;
-  }
-  __syncthreads();
-
-  // ---- gather: the warpAffine of the tile (and its halo) into LDS ----
-  const uint8_t* src = a.frames + (int64_t)fi * a.fstride;
-  const int side = kTile + 2 * halo;
-  for (int p = tid; p < side * side; p += 256) {
-    const int r = p / side - halo, c = p - (p / side) * side - halo;   // tile coordinates in [-1, 28]
-    const int cx = ox + c, cy = oy + r;
-    if (cx < 0 || cx >= S || cy < 0 || cy >= S) continue;              // outside the crop: never read back
-    const long X = (rowX[r + 1] + colA[c + 1]) >> 5, Y = (rowY[r + 1] + colB[c + 1]) >> 5;
-    const long sx = X >> 5, sy = Y >> 5;
-    const float fx = (float)(X & 31) * (1.f / 32.f), fy = (float)(Y & 31) * (1.f / 32.f);
-    const float wx[2] = {f_sub(1.f, fx), fx}, wy[2] = {f_sub(1.f, fy), fy};
-    int acc[3] = {0, 0, 0};
-#pragma unroll
-    for (int ky = 0; ky < 2; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 2; ++kx) {
-        const long tx = sx + kx, ty = sy + ky;
-        if (tx < 0 || tx >= a.W || ty < 0 || ty >= a.H) continue;      // constant 0 border
-        const int wi = cv_warp_weight_u8(wy[ky], wx[kx]);
-        const uint8_t* s = src + (ty * (int64_t)a.W + tx) * 3;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) acc[ch] += (int)s[ch] * wi;
-      }
-    uint8_t* t = tile + (r + 1) * kRow + 4 + 3 * c;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const int v = (acc[ch] + (1 << 14)) >> 15;
-      t[ch] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-    }
-  }
-  __syncthreads();
-
-  // ---- the crop tile: packed dword stores where the rows allow it ----
-  if (a.crops) {
-    const int tw = min(kTile, S - ox), th = min(kTile, S - oy);
-    uint8_t* dst = a.crops + (int64_t)n * a.cstride + ((int64_t)oy * S + ox) * 3;
-    const int64_t pitch = (int64_t)S * 3;
-    const bool packed = (((uintptr_t)a.crops | (uint64_t)a.cstride | (uint64_t)pitch | (uint64_t)(tw * 3)) & 3) == 0;
-    if (packed) {
-      const int ndw = tw * 3 / 4;
-      for (int i = tid; i < th * ndw; i += 256) {
-        const int r = i / ndw, j = i - r * ndw;
-        *(uint32_t*)(dst + r * pitch + 4 * j) = *(const uint32_t*)(tile + (r + 1) * kRow + 4 + 4 * j);
-      }
-    } else {
-      const int nb = tw * 3;
-      for (int i = tid; i < th * nb; i += 256) {
-        const int r = i / nb, j = i - r * nb;
-        dst[r * pitch + j] = tile[(r + 1) * kRow + 4 + j];
-      }
-    }
-  }
-
-  // ---- cv2.resize out of LDS: one thread makes 4 pixels = 3 dwords ----
-  if (a.resized) {
-    const int R = a.R;
-    const int ow = min(kOut, R - txi * kOut), oh = min(kOut, R - tyi * kOut);   // multiples of 8
-    const int row = tid >> 3, q = (tid & 7) * 4;
-    if (row < oh && q < ow) {
-      const LocalTap ty = rzr[row];
-      union { uint8_t b[12]; uint32_t d[3]; } o;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const LocalTap tx = rzc[q + k];
-        const uint8_t* r0 = tile + ty.o0;
-        const uint8_t* r1 = tile + ty.o1;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-          const int D0 = (int)r0[tx.o0 + ch] * tx.w0 + (int)r0[tx.o1 + ch] * tx.w1;
-          const int D1 = (int)r1[tx.o0 + ch] * tx.w0 + (int)r1[tx.o1 + ch] * tx.w1;
-          int v = ((((D0 >> 4) * ty.w0) >> 16) + (((D1 >> 4) * ty.w1) >> 16) + 2) >> 2;
-          o.b[k * 3 + ch] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-        }
-      }
-      uint8_t* dst = a.resized + (int64_t)n * a.rstride + ((int64_t)(tyi * kOut + row) * R + txi * kOut + q) * 3;
-      if ((((uintptr_t)a.resized | (uint64_t)a.rstride) & 3) == 0) {   // R is a multiple of 8: rows are dword-aligned
-#pragma unroll
-        for (int k = 0; k < 3; ++k) ((uint32_t*)dst)[k] = o.d[k];
-      } else {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) dst[k] = o.b[k];
-      }
-    }
-  }
+  const FrameSource src{a.frames + (int64_t)fi * a.fstride, a.H, a.W};
+  align_tile(src, a.maps + (int64_t)n * 6, n, a.out);
 }
 
 }  // namespace
@@ -196,8 +70,8 @@ extern "C" int ghost_align_crops_u8(const uint8_t* frames, int64_t frame_stride,
   const int tiles = (S + kTile - 1) / kTile;
   if ((int64_t)tiles * tiles > 0x7fffffffLL)
     return ghost::set_last_error(GHOST_EINVAL, "ghost_align_crops_u8: bad sizes");
-  AlignArgs a{frames, frame_stride, F, H, W, frame_index, maps, valid, S, crops, crop_stride,
-              resized, resized_stride, resized ? R : 0, tiles};
+  AlignArgs a{frames, frame_stride, F, H, W, frame_index, maps, valid,
+              {S, crops, crop_stride, resized, resized_stride, resized ? R : 0, tiles}};
   dim3 grid((unsigned)(tiles * tiles), (unsigned)N);
   hipLaunchKernelGGL(align_crops_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
   const int rc = (int)hipGetLastError();

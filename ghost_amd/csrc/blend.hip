@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blend_pixel.h"
 #include "cv_warp.h"
 #include "ghost_amd.h"
 #include "ghost_common.h"
@@ -39,34 +40,8 @@ __global__ void __launch_bounds__(256) blend_kernel(const BlendArgs a) {
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   if (p >= (long)a.H * a.W) return;
   const int y = (int)(p / a.W), x = (int)(p - (long)y * a.W);
-  const float* m = a.mats + f * 6;
-  const float ix = fmaf(m[0], (float)x, fmaf(m[1], (float)y, m[2]));
-  const float iy = fmaf(m[3], (float)x, fmaf(m[4], (float)y, m[5]));
-  if (!(ix > -1.f && ix < (float)a.Ws && iy > -1.f && iy < (float)a.Hs)) return;   // every tap outside
-  // grid_sampler_2d bilinear (zeros padding): corner weights as PyTorch forms them
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy;
-  const float nw = (fx + 1.f - ix) * (fy + 1.f - iy), ne = (ix - fx) * (fy + 1.f - iy);
-  const float sw = (fx + 1.f - ix) * (iy - fy), se = (ix - fx) * (iy - fy);
-  const int tx[4] = {x0, x0 + 1, x0, x0 + 1}, ty[4] = {y0, y0, y0 + 1, y0 + 1};
-  const float tw[4] = {nw, ne, sw, se};
-  const uint8_t* sw8 = a.swaps + f * a.sstride;
-  const float* mk = a.masks + f * a.mstride;
-  float ms = 0.f, sv[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    if (tx[t] < 0 || tx[t] >= a.Ws || ty[t] < 0 || ty[t] >= a.Hs) continue;
-    const long o = (long)ty[t] * a.Ws + tx[t];
-    ms += mk[o] * tw[t];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) sv[c] += (float)sw8[o * 3 + c] * tw[t];
-  }
-  uint8_t* fr = a.frames + f * a.fstride + p * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float v = ms * sv[c] + (1.f - ms) * (float)fr[c];
-    fr[c] = (uint8_t)(int)fminf(fmaxf(v, 0.f), 255.f);   // .type(torch.uint8) of a value in [0, 255]
-  }
+  blend_pixel(x, y, a.mats + f * 6, a.swaps + f * a.sstride, a.Hs, a.Ws, a.masks + f * a.mstride,
+              a.frames + f * a.fstride + p * 3);
 }
 
 // cv2.resize(src, (Wd, Hd)) INTER_LINEAR on uint8 3-channel images (video_processing.py:212: the 256x256 swap

@@ -317,6 +317,38 @@ int ghost_align_crops_u8(const uint8_t* frames, int64_t frame_stride, int F, int
                          const double* maps, const int32_t* valid, int N, int S, uint8_t* crops, int64_t crop_stride,
                          uint8_t* resized, int64_t resized_stride, int R, void* stream);
 
+/* ---- ROI video path: only each face's rectangle crosses the host link ----
+ * The frames stay on the host.  Per (identity, frame) the rectangle (x0, y0, w, h) of the frame that
+ * cv2.warpAffine(frame, M, (S, S)) reads and the paste-back can write (ghost_amd.inference.roi.face_rois) lives in
+ * patch p of a device canvas patches [Np,Ph,Pw,3] u8 (patch_stride bytes apart, w <= Pw, h <= Ph), rectangle pixel
+ * (px, py) at patches + p patch_stride + (py Pw + px) 3.
+ * ghost_roi_copy_u8 issues one hipMemcpy2DAsync per patch on the stream between frame_ptrs_host[p] + (y0 W + x0) 3
+ * (pitch 3 W; frame_ptrs_host[p] = the [H,W,3] host frame patch p belongs to, pinned for an asynchronous copy) and
+ * the patch (pitch 3 Pw), 3 w bytes by h rows: host to device with to_device != 0, back otherwise.  rects_host is
+ * the host int32 [Np][4] array; every rectangle is checked before the first copy (inside the frame, no larger than
+ * the canvas: GHOST_EINVAL, nothing copied); an empty rectangle (w or h 0) is skipped.  Np == 0 returns GHOST_OK.
+ * ghost_align_crops_roi_u8 = ghost_align_crops_u8 with crop n taken from patch patch_index[n]: a tap at frame pixel
+ * (tx, ty) is read at (tx - x0, ty - y0) of the patch when it lies inside the rectangle and is 0 otherwise, which is
+ * cv2's constant border because the rectangle lies inside the frame and covers every in-frame tap.  rects
+ * (int32 [Np][4]) and patch_index (int32 [N]) are device arrays, maps the same double frame-coordinate maps; w and h
+ * are clamped to the canvas, and a row with patch_index[n] outside [0, Np) or valid[n] == 0 is left untouched.  The
+ * outputs, the (S, R) rule, N <= 65535 and N == 0 are those of ghost_align_crops_u8; the crops are its bytes.
+ * ghost_blend_swaps_roi_u8 = ghost_blend_swaps_u8 over the rectangles only: entry n composites swaps[n] / masks[n]
+ * through mats[n] (fp32 [N][2][3], frame coordinates) into patch patch_index[n], one thread per rectangle pixel,
+ * writing the bytes the full-frame kernel writes.  The composite is an in-place read-modify-write: the entries of
+ * one call must reference distinct patches (several identities on one patch: one call each, in the reference's
+ * order).  N <= 65535; N == 0 returns GHOST_OK without a launch.  No call allocates or synchronises. */
+int ghost_roi_copy_u8(uint8_t* patches, int64_t patch_stride, int Np, int Ph, int Pw, const int32_t* rects_host,
+                      uint8_t* const* frame_ptrs_host, int H, int W, int to_device, void* stream);
+int ghost_align_crops_roi_u8(const uint8_t* patches, int64_t patch_stride, int Np, int Ph, int Pw,
+                             const int32_t* rects, const int32_t* patch_index, const double* maps,
+                             const int32_t* valid, int N, int S, uint8_t* crops, int64_t crop_stride, uint8_t* resized,
+                             int64_t resized_stride, int R, void* stream);
+int ghost_blend_swaps_roi_u8(uint8_t* patches, int64_t patch_stride, int Np, int Ph, int Pw, const int32_t* rects,
+                             const int32_t* patch_index, int N, const uint8_t* swaps, int64_t swap_stride, int Hs,
+                             int Ws, const float* masks, int64_t mask_stride, const float* mats, const int32_t* valid,
+                             void* stream);
+
 /* ---- face masks (face_mask_static, utils/inference/masks.py:38-107) ----
  * Host, CPU only (no device pointers): for F frames of 106 float32 landmarks [F][106][2] and their
  * (erode, sigmaX, sigmaY) params [F][3] (face_mask_static's, masks.py:43-65), expand_eyebrows on the int32
