@@ -94,6 +94,8 @@ _SIGS = {
                                        C.POINTER(i32), vp, i64, vp]),
     "ghost_conv3x3_narrow_nhwc": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, i32, vp,
                                         vp]),
+    "ghost_plan_log": (i32, [i32]),
+    "ghost_plan_log_read": (i64, [C.c_char_p, i64]),
 }
 
 
@@ -132,6 +134,21 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load().ghost_last_error().decode(errors="replace")
         raise RuntimeError(f"ghost_amd{(' ' + what) if what else ''} failed (rc={rc}): {msg}")
+
+
+def plan_log(enable: bool) -> None:
+    """Start (clearing it) or stop the native plan log (ghost_plan_log, test support)."""
+    check(load().ghost_plan_log(1 if enable else 0), "plan_log")
+
+
+def plan_log_read() -> list:
+    """The plan signatures recorded since ``plan_log(True)``, one per launch, in launch order."""
+    lib = load()
+    while True:
+        need = lib.ghost_plan_log_read(None, 0)
+        buf = C.create_string_buffer(int(need))
+        if lib.ghost_plan_log_read(buf, need) <= need:     # (another thread may have launched in between)
+            return [s for s in buf.value.decode().split("\n") if s]
 
 
 def gdtype(t: torch.dtype) -> int:

@@ -13,6 +13,7 @@
 // (<= 16x16 at batch 64) use the generic GEMM + separate mask path instead.
 #include "aad_fused.h"
 #include "ghost_common.h"
+#include "plan_log.h"
 
 namespace ghost {
 
@@ -253,6 +254,7 @@ int aad_fused(int dt, const void* za, int lda, int Ca, const void* w, int Kpad, 
   a.M = B * HW; a.slope = slope;
   constexpr int BM = 64;
   dim3 grid((unsigned)(a.M / BM));
+  GHOST_PLAN_LOG("aad_fused t=%s BM=%d C=%d Ca=%d", plan_dt(dt), BM, C, Ca);
   if (dt == GHOST_BF16) {
     const size_t lds = lds_bytes<bf16, BM>(C);
     hipLaunchKernelGGL((aad_fused_kernel<bf16, BM>), grid, dim3(256), lds, s, a);

@@ -21,6 +21,7 @@
 
 #include "aad_v3.h"
 #include "ghost_common.h"
+#include "plan_log.h"
 #include "tap_rows.h"
 #include "up2x.h"
 
@@ -1294,11 +1295,16 @@ static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
   a.v5_ipw = v5_takes(d, zpm);
   a.v5_flags = GHOST_KNOB("GHOST_V5_FLAGS", 3);
   static const int v5_asm = GHOST_KNOB("GHOST_V5_ASM", 1);
+  // plan log: the kernel and every parameter chosen above (a.PPW and a.v5_ipw as the launch uses them)
+#define GHOST_AAD_LOG(kernel)                                                                                  \
+  GHOST_PLAN_LOG("%s t=%s C=%d Ca=%d L=%d up=%d zpm=%d slope0=%d v5_ipw=%d ppw=%d", kernel, plan_dt(gdt<T>()),   \
+                 d.C, d.Ca, d.L, (int)up, zpm, d.slope == 0.f, a.v5_ipw, a.PPW)
   if (a.v5_ipw && d.C == 128) {
     a.PPW = 1024;
     grid = dim3((unsigned)((long)d.B * d.HW / 1024 / a.v5_ipw));
 #define GHOST_V5W(l)                                                                             \
     if (d.L == l) {                                                                              \
+      GHOST_AAD_LOG("aad_v5_wide");                                                              \
       if (d.slope == 0.f)                                                                        \
         hipLaunchKernelGGL((aad_v5_wide_kernel<T, 64, l, true>), grid, dim3(1024), 0, s, a);      \
       else                                                                                       \
@@ -1314,6 +1320,7 @@ static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
     grid = dim3(grid.x / a.v5_ipw);
 #define GHOST_V5(ca, l)                                                                          \
     if (d.Ca == ca && d.L == l && !zpm) {                                                        \
+      GHOST_AAD_LOG("aad_v5");                                                                   \
       if (d.slope == 0.f)                                                                        \
         hipLaunchKernelGGL((aad_v5_kernel<T, ca, l, true, 0, false>), grid, dim3(kWaves * 64), 0, s, a); \
       else                                                                                       \
@@ -1325,6 +1332,7 @@ static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
 #undef GHOST_V5
 #define GHOST_V5Z(ca, zm)                                                                        \
     if (d.Ca == ca && d.L == 2 && zpm == zm) {                                                   \
+      GHOST_AAD_LOG(v5_asm ? "aad_v5z_asm" : "aad_v5z");                                          \
       if (v5_asm)                                                                                \
         hipLaunchKernelGGL((aad_v5_kernel<T, ca, 2, true, zm, true>), grid, dim3(kWaves * 64), 0, s, a); \
       else                                                                                       \
@@ -1341,6 +1349,7 @@ static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
   if (use_v4 && up && d.C == 64 && a.PPW % 256 == 0 && d.ldh % 8 == 0) {
 #define GHOST_V4(ca, l, u)                                                                       \
     if (d.Ca == ca && d.L == l && up == u && !zpm) {                                             \
+      GHOST_AAD_LOG("aad_v4");                                                                   \
       if (d.slope == 0.f)                                                                        \
         hipLaunchKernelGGL((aad_v4_kernel<ca, l, u, true>), grid, dim3(kWaves * 64), dyn_lds, s, a); \
       else                                                                                       \
@@ -1353,6 +1362,7 @@ static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
     // AADBlk8's block-input pair with tap partials: layer 1 (last_add_block, nb >= 2) or both (nb = 1)
 #define GHOST_V4Z(ca, zm)                                                                        \
     if (d.Ca == ca && d.L == 2 && zpm == zm) {                                                   \
+      GHOST_AAD_LOG("aad_v4z");                                                                  \
       hipLaunchKernelGGL((aad_v4_kernel<ca, 2, true, true, zm>), grid, dim3(kWaves * 64), 0, s, a); \
       if (d.version_out) *d.version_out = 4;                                                     \
       return (int)hipGetLastError();                                                             \
@@ -1363,6 +1373,7 @@ static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
   }
   if (zpm) {   // the non-upsampled forms with tap partials (AADBlk8's last add_block; fuse_upsample off)
     if (d.C == 64 && d.L == 1 && !up && zpm == 1 && (d.Ca == 64 || d.Ca == 32)) {
+      GHOST_AAD_LOG("aad_v3_zp1");
       if (d.Ca == 64)
         hipLaunchKernelGGL((aad_v3_zp1_kernel<T, 64>), grid, dim3(kWaves * 64), 0, s, a);
       else
@@ -1371,6 +1382,7 @@ static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
     }
 #define GHOST_V3Z(ca, l, zm)                                                                     \
     if (d.C == 64 && d.Ca == ca && d.L == l && !up && zpm == zm) {                               \
+      GHOST_AAD_LOG("aad_v3z");                                                                  \
       hipLaunchKernelGGL((aad_v3_kernel<T, 64, ca, l, false, zm>), grid, dim3(kWaves * 64), 0, s, a); \
       return (int)hipGetLastError();                                                             \
     }
@@ -1381,11 +1393,13 @@ static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
   }
 #define GHOST_V3(c, ca, l, u)                                                                   \
   if (d.C == c && d.Ca == ca && d.L == l && up == u) {                                          \
+    GHOST_AAD_LOG("aad_v3");                                                                    \
     hipLaunchKernelGGL((aad_v3_kernel<T, c, ca, l, u>), grid, dim3(kWaves * 64), 0, s, a);         \
     return (int)hipGetLastError();                                                              \
   }
 #define GHOST_V3W(c, ca, l, u)                                                                  \
   if (d.C == c && d.Ca == ca && d.L == l && up == u) {                                          \
+    GHOST_AAD_LOG("aad_v3_wide");                                                               \
     hipLaunchKernelGGL((aad_v3_wide_kernel<T, c, ca, l, u>), grid, dim3(kWaves * 64), 0, s, a);    \
     return (int)hipGetLastError();                                                              \
   }
@@ -1401,6 +1415,7 @@ static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
   GHOST_V3W(256, 128, 1, false) GHOST_V3W(256, 64, 1, false)
 #undef GHOST_V3W
 #undef GHOST_V3
+#undef GHOST_AAD_LOG
   return -1;
 }
 

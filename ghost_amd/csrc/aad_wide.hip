@@ -12,6 +12,7 @@
 
 #include "aad_wide.h"
 #include "ghost_common.h"
+#include "plan_log.h"
 
 namespace ghost {
 
@@ -368,6 +369,7 @@ static int aad_wide_t(const AadWideDesc& d, hipStream_t s) {
   a.lda = d.lda; a.ldh = d.ldh; a.ldo = d.ldo; a.id_ld = d.id_ld; a.HW = d.HW; a.slope = d.slope;
   if (aad_gemm_ok(d)) {
     dim3 g((unsigned)((long)d.B * d.HW / 256 * (d.C / 128)));
+    GHOST_PLAN_LOG("aad_gemm t=%s C=%d Ca=%d", plan_dt(gdt<T>()), d.C, d.Ca);
     hipLaunchKernelGGL((aad_gemm_kernel<T, 512>), g, dim3(256), 0, s, a, d.C);
     return (int)hipGetLastError();
   }
@@ -376,6 +378,7 @@ static int aad_wide_t(const AadWideDesc& d, hipStream_t s) {
   dim3 grid((unsigned)(a.nblk * (d.C / 64)));
 #define GHOST_W(c, ca)                                                                 \
   if (d.C == c && d.Ca == ca) {                                                        \
+    GHOST_PLAN_LOG("aad_wide t=%s C=%d Ca=%d ppw=%d", plan_dt(gdt<T>()), c, ca, a.PPW); \
     hipLaunchKernelGGL((aad_wide_kernel<T, c, ca>), grid, dim3(kWideWaves * 64), 0, s, a); \
     return (int)hipGetLastError();                                                     \
   }
@@ -384,6 +387,7 @@ static int aad_wide_t(const AadWideDesc& d, hipStream_t s) {
 #undef GHOST_W
 #define GHOST_WD(c, ca)                                                                     \
   if (d.C == c && d.Ca == ca) {                                                             \
+    GHOST_PLAN_LOG("aad_wide_deep t=%s C=%d Ca=%d ppw=%d", plan_dt(gdt<T>()), c, ca, a.PPW); \
     hipLaunchKernelGGL((aad_wide_deep_kernel<T, c, ca>), grid, dim3(kWideWaves * 64), 0, s, a); \
     return (int)hipGetLastError();                                                          \
   }

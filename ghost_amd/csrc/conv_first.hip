@@ -10,6 +10,7 @@
 // kernel), so the FMA loop never converts a weight.
 #include "conv_first.h"
 #include "ghost_common.h"
+#include "plan_log.h"
 
 namespace ghost {
 
@@ -194,6 +195,7 @@ int conv_first(const ConvDesc& d, void* ws, size_t ws_bytes, hipStream_t s) {
     m.Hi = d.Hi; m.Wi = d.Wi; m.Ho = Ho; m.Wo = Wo; m.Kpad = d.Kpad; m.ldy = d.ldy; m.slope = d.slope;
     m.M = (long)d.B * Ho * Wo;
     const dim3 g((unsigned)(((m.M / 64 + kFirstChunks - 1) / kFirstChunks + 3) / 4));
+    GHOST_PLAN_LOG("first mfma t=%s chunktail=%d", plan_dt(d.ti), (m.M / 64) % (4 * kFirstChunks) != 0);
     if (d.ti == GHOST_BF16)
       hipLaunchKernelGGL(conv_first_mfma_kernel<bf16>, g, dim3(256), 0, s, m);
     else
@@ -216,6 +218,7 @@ int conv_first(const ConvDesc& d, void* ws, size_t ws_bytes, hipStream_t s) {
   a.Kpad = d.Kpad; a.ldy = d.ldy; a.slope = d.slope;
   a.M = (long)d.B * a.Ho * a.Wo;
   dim3 grid((unsigned)((a.M + 255) / 256));
+  GHOST_PLAN_LOG("first scalar t=%s mtail=%d", plan_dt(d.ti), a.M % 256 != 0);
   if (d.ti == GHOST_BF16)
     hipLaunchKernelGGL((conv_first_kernel<bf16, 32>), grid, dim3(256), 0, s, a);
   else if (d.ti == GHOST_F16)
@@ -376,6 +379,8 @@ int conv_stem3x3(const ConvDesc& d, hipStream_t s) {
   a.H = d.Hi; a.W = d.Wi; a.Kpad = d.Kpad; a.ldy = d.ldy; a.ldy2 = d.ldy2; a.slope = d.slope;
   a.M = d.B * d.Hi * d.Wi;
   const long waves = ((long)(a.M + 63) / 64 + kStemChunks - 1) / kStemChunks;
+  GHOST_PLAN_LOG("stem3x3 t=bf16 y2=%d mtail=%d chunktail=%d", d.y2 != nullptr, a.M % 64 != 0,
+                 ((a.M + 63) / 64) % (4 * kStemChunks) != 0);
   hipLaunchKernelGGL(conv_stem3x3_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }

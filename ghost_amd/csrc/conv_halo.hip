@@ -22,6 +22,7 @@
 
 #include "conv_halo.h"
 #include "ghost_common.h"
+#include "plan_log.h"
 
 namespace ghost {
 
@@ -55,6 +56,10 @@ using HaloWide = HaloCfg<16, 32, 8, 1>;    // W % 32 == 0: 16 x 32 tile, 8 waves
 using HaloSmall = HaloCfg<16, 16, 4, 1>;   // W == 16: 16 x 16 tile, 4 waves, 57 KB LDS
 using HaloImg8 = HaloCfg<8, 8, 4, 1, 4>;   // 8 x 8 images, four per tile, 4 waves, 61 KB per stage
 using HaloPair = HaloCfg<16, 16, 8, 1, 2>; // a 16 x 16 window of two samples, 8 waves, 77 KB per stage
+// the configuration's name in the plan log
+template <class G> static const char* halo_cfg_name() {
+  return G::IMG == 4 ? "Img8" : G::IMG == 2 ? "Pair" : G::TW == 32 ? "Wide" : "Small";
+}
 
 struct HaloArgs {
   const void* x;   // 16-bit storage (bf16 or fp16: the kernels' T)
@@ -1035,6 +1040,7 @@ static int haloT_launch(const ConvDesc& d, hipStream_t s) {
   a.ldy = d.ldy; a.ldres = d.ldres; a.slope = d.slope;
   a.tiles_x = d.Wi / HaloTCfg<BN>::TIW; a.tiles_y = d.Hi / HaloTCfg<BN>::TIH; a.nNt = (d.N + BN - 1) / BN;
   const long ntiles = (long)d.B * a.tiles_x * a.tiles_y * a.nNt;
+  GHOST_PLAN_LOG("convT_halo t=%s BN=%d Cin=%d N=%d res=%d", plan_dt(gdt<T>()), BN, d.Cin, d.N, d.res != nullptr);
   hipLaunchKernelGGL((convT_halo_kernel<T, BN>), dim3((unsigned)ntiles), dim3(512), 0, s, a);
   return (int)hipGetLastError();
 }
@@ -1101,6 +1107,8 @@ static int halo_launch(const ConvDesc& d, hipStream_t s) {
   a.tiles_x = (d.Wi + G::TW - 1) / G::TW; a.tiles_y = (d.Hi + G::TH - 1) / G::TH;
   a.nNt = (d.N + G::BN - 1) / G::BN;
   a.ntiles = d.B * a.tiles_x * a.tiles_y * a.nNt;
+  GHOST_PLAN_LOG("halo t=%s tile=%s Cin=%d N=%d overhang=%d", plan_dt(gdt<T>()), halo_cfg_name<G>(), d.Cin, d.N,
+                 d.Hi % G::TH != 0 || d.Wi % G::TW != 0);
   hipLaunchKernelGGL((conv3x3_halo_kernel<T, G>), dim3((unsigned)a.ntiles), dim3(G::NW * 64), 0, s, a);
   return (int)hipGetLastError();
 }
@@ -1168,11 +1176,14 @@ static int halo_pp_launch(const ConvDesc& d, hipStream_t s) {
   }
 #endif
   constexpr bool CAN_ST = G::TW != 16;   // the partials come from exact 16 x 32 tiles or whole 8 x 8 images
-#define GHOST_PP(R, ST, NB) \
+#define GHOST_PP(R, ST, NB)                                                                                       \
+  GHOST_PLAN_LOG("halo_pp t=%s tile=%s RESW=%d STATS=%d NCB=%d N=%d overhang=%d uneven=%d", plan_dt(gdt<T>()),    \
+                 halo_cfg_name<G>(), (int)R, (int)ST, NB, d.N, d.Hi % G::TH != 0 || d.Wi % G::TW != 0,            \
+                 a.ntiles % g != 0);                                                                              \
   hipLaunchKernelGGL((conv3x3_halo_pp_kernel<T, G, R, ST, NB>), dim3((unsigned)g), dim3(NT), 0, s, a)
 #define GHOST_PP2(R, NB)                                  \
   if constexpr (CAN_ST) {                                  \
-    if (a.in_part) GHOST_PP(R, CAN_ST, NB); else GHOST_PP(R, false, NB); \
+    if (a.in_part) { GHOST_PP(R, CAN_ST, NB); } else { GHOST_PP(R, false, NB); } \
   } else {                                                 \
     if (a.in_part) return -1;                              \
     GHOST_PP(R, false, NB);                                \

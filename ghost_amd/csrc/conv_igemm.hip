@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "conv_igemm.h"
+#include "plan_log.h"
 #include "conv_first.h"
 #include "conv_halo.h"
 #include "conv_s2.h"
@@ -174,6 +175,7 @@ GHOST_DEV void split_fixup(const ConvArgs& a, int tid, int tile_id, int m0, int 
 // the GEMM kernel
 // ---------------------------------------------------------------------------
 enum { KEPI_STD = 0, KEPI_AAD = 1, KEPI_SPLIT = 2 };
+inline const char* kepi_name(int epi) { return epi == KEPI_STD ? "STD" : epi == KEPI_AAD ? "AAD" : "SPLIT"; }
 
 // wave layout: 4 waves as 2x2 (BM <= 128, BN >= 32) or 4x1 (BM = 256 or a 16-wide N tile)
 template <int BM, int BN> struct WaveGrid { static constexpr int WN = (BM <= 128 && BN >= 32) ? 2 : 1, WM = 4 / WN; };
@@ -480,9 +482,11 @@ void launch_reduce(const ConvArgs& a, int ncols, int npar, hipStream_t s) {
   const long total = (long)a.M * ncols;
   if (vec && ncols % 4 == 0 && a.NT % 4 == 0) {
     dim3 grid((unsigned)((total / 4 + 255) / 256), 1, npar);
+    GHOST_PLAN_LOG("splitk_reduce4 to=%s epi=%s", plan_dt(gdt<TO>()), kepi_name(EPI));
     hipLaunchKernelGGL((splitk_reduce4_kernel<TO, EPI>), grid, dim3(256), 0, s, a);
   } else {
     dim3 grid((unsigned)((total + 255) / 256), 1, npar);
+    GHOST_PLAN_LOG("splitk_reduce to=%s epi=%s", plan_dt(gdt<TO>()), kepi_name(EPI));
     hipLaunchKernelGGL((splitk_reduce_kernel<TO, EPI>), grid, dim3(256), 0, s, a);
   }
 }
@@ -845,9 +849,24 @@ ConvArgs make_args(const ConvDesc& d, const Plan& p, float* partial) {
   return a;
 }
 
+// plan log: the edge classes of a GEMM launch (plan_log.h), for a kernel whose ring prologue holds `stages` - 1
+// K steps (the register-staged kernel: 2).  No M, no split count: only the classes they fall in.
+struct PlanEdges { char s[128]; };
+PlanEdges plan_edges(const ConvArgs& a, const Plan& p, int bk, int stages) {
+  PlanEdges e;
+  const int nk = a.Kpad / bk, last = nk % a.kt_per_split;
+  snprintf(e.s, sizeof(e.s), "split=%d ragged=%d short=%d lastshort=%d fixup=%s mtail=%d ntail=%d%s", a.nsplit > 1,
+           last != 0, a.kt_per_split < stages - 1, last != 0 && last < stages - 1,
+           !a.sem ? "none" : a.fuse == 2 ? "aad" : "std", a.M % p.BM != 0, a.N % p.BN != 0,
+           a.sem ? (a.M < p.BM ? " fixrows=M" : " fixrows=BM") : "");
+  return e;
+}
+
 template <typename TI, typename TO, int BM, int BN, int BK, int EPI, bool FAST>
 void launch_gemm(const ConvArgs& a, const Plan& p, hipStream_t s) {
   dim3 grid(p.nMt * p.nNt, p.nsplit, p.npar);
+  GHOST_PLAN_LOG("igemm ti=%s to=%s %dx%dx%d fast=%d epi=%s kind=%s %s", plan_dt(gdt<TI>()), plan_dt(gdt<TO>()), BM, BN,
+                 BK, (int)FAST, kepi_name(EPI), a.deconv ? "T4S2" : "FWD", plan_edges(a, p, BK, 2).s);
   hipLaunchKernelGGL((conv_igemm_kernel<TI, TO, BM, BN, BK, EPI, FAST>), grid, dim3(256), 0, s, a);
 }
 
@@ -895,8 +914,12 @@ bool launch_glds(const ConvArgs& a, const Plan& p, hipStream_t s) {
   static const int ws = GHOST_KNOB("GHOST_CONV_WS", 1);
   const int stages = p.stages > 0 ? p.stages : stages_knob;
   dim3 grid(p.nMt * p.nNt, p.nsplit, p.npar);
+#define GHOST_G_LOG(bm, bn, st, wsl)                                                                       \
+  GHOST_PLAN_LOG("glds t=%s %dx%d stages=%d ws=%d epi=%s kind=%s %s", plan_dt(gdt<T>()), bm, bn, st, wsl,    \
+                 kepi_name(EPI), a.deconv ? "T4S2" : "FWD", plan_edges(a, p, 32, st).s)
   if constexpr (EPI == KEPI_AAD) {
     if (p.BM == 128 && p.BN == 128 && stages == 8) {
+      GHOST_G_LOG(128, 128, 8, ws ? 4 : 0);
       if (ws)
         hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, 8, EPI, 4>), grid, dim3(512), 0, s, a);
       else
@@ -904,6 +927,7 @@ bool launch_glds(const ConvArgs& a, const Plan& p, hipStream_t s) {
       return true;
     }
     if (p.BM == 128 && p.BN == 128 && stages == 3 && ws) {
+      GHOST_G_LOG(128, 128, 3, 4);
       hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, 3, EPI, 4>), grid, dim3(512), 0, s, a);
       return true;
     }
@@ -911,6 +935,7 @@ bool launch_glds(const ConvArgs& a, const Plan& p, hipStream_t s) {
   }
 #define GHOST_G(bm, bn, st)                                                                      \
   if (p.BM == bm && p.BN == bn && stages == st) {                                                \
+    GHOST_G_LOG(bm, bn, st, ws ? 4 : 0);                                                          \
     if (ws)                                                                                       \
       hipLaunchKernelGGL((conv_glds_kernel<T, bm, bn, st, EPI, 4>), grid, dim3(512), 0, s, a);      \
     else                                                                                          \
@@ -921,6 +946,7 @@ bool launch_glds(const ConvArgs& a, const Plan& p, hipStream_t s) {
   GHOST_G(128, 128, 4) GHOST_G(256, 64, 4) GHOST_G(128, 64, 4) GHOST_G(64, 128, 4)
   GHOST_G(128, 128, 3) GHOST_G(256, 64, 3) GHOST_G(128, 64, 3) GHOST_G(64, 128, 3)
 #undef GHOST_G
+#undef GHOST_G_LOG
   return false;
 }
 
@@ -935,6 +961,7 @@ int dispatch_types(const ConvDesc& d, const ConvArgs& a, const Plan& p, hipStrea
     if (rc) return rc;
     const long total = (long)p.M * d.N;
     dim3 grid((unsigned)((total + 255) / 256), 1, p.npar);
+    GHOST_PLAN_LOG("splitk_reduce to=f32 epi=STD from=%s", plan_dt(gdt<TI>()));
     hipLaunchKernelGGL((splitk_reduce_kernel<float, KEPI_STD>), grid, dim3(256), 0, s, a);
     return 0;
   } else {

@@ -24,6 +24,7 @@
 
 #include "conv_s2.h"
 #include "ghost_common.h"
+#include "plan_log.h"
 
 namespace ghost {
 namespace {
@@ -266,6 +267,8 @@ int conv_s2_patch(const ConvDesc& d, hipStream_t s) {
   a.y2 = d.y2; a.ldy2 = d.ldy2; a.scale2 = d.scale2; a.shift2 = d.shift2;
   dim3 grid((unsigned)(d.B * a.tiles_per_img), (unsigned)(d.N / BN));
   const bool h16 = d.ti == GHOST_F16;
+  GHOST_PLAN_LOG("s2_patch t=%s K=%d ncb=%d N=%d overhang=%d", plan_dt(d.ti), K, a.ncb, d.N,
+                 a.Ho % TH != 0 || a.Wo % TW != 0);
   if (K == 4) {
     if (h16) hipLaunchKernelGGL((conv_s2_patch_kernel<_Float16, 4>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((conv_s2_patch_kernel<bf16, 4>), grid, dim3(256), 0, s, a);

@@ -361,6 +361,19 @@ int64_t ghost_face_masks_workspace_bytes(int F, int H, int W);
 int ghost_face_masks(const int32_t* poly, const int32_t* nv, const int32_t* params, int F, int H, int W, float* masks,
                      int64_t mask_stride, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- plan log (test support) ----
+ * While enabled, every launcher that chooses among kernel variants by shape (the conv dispatcher and everything
+ * it dispatches to, the AAD launchers) appends one text signature per launch: the kernel with every template or
+ * runtime parameter the host chose and the edge classes of the launch (split-K: count class, ragged last split,
+ * split shorter than the ring's prologue, fix-up kind, reduction form; M / N tails; an uneven persistent grid).
+ * A signature holds no batch size, row count or pointer, so every batch that selects the same plan yields the same
+ * text.  Process-wide, guarded by a mutex; disabled it costs one relaxed atomic load per launch.
+ * ghost_plan_log(1) clears the log and starts recording, ghost_plan_log(0) stops.  ghost_plan_log_read copies
+ * the newline-separated signatures in launch order into buf (at most cap bytes, NUL-terminated) and returns the
+ * bytes needed including the NUL; buf = NULL asks for the size. */
+int ghost_plan_log(int enable);
+int64_t ghost_plan_log_read(char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

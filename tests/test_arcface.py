@@ -162,11 +162,16 @@ def test_bf16_each_stage_matches_storage_emulation(arch, B):
     runs the two-sample halo window (HaloPair) at 56x56 / 28x28 / 14x14, B = 256 also the deep LDS-DMA ring at
     7x7 (M = 12 544); two rows of each are checked."""
     m = net(arch, compute_dtype=torch.bfloat16)
+    check_bf16_stages(m, arch, B, [0, 1] if B == 2 else [0, 77] if B == 128 else [0, 201])
+
+
+def check_bf16_stages(m, arch, B, rows):
+    """The per-stage teacher-forced gate on ``rows`` of a batch of B (also tests/test_batch_sweep.py)."""
     layers, p = A.LAYERS[arch], weights(arch)
     x = torch.from_numpy(np.random.Generator(np.random.PCG64(6)).uniform(-1, 1, (B, 3, 112, 112)).astype(np.float32))
     emb, taps = m.forward_taps(x.to(DEV))
     torch.cuda.synchronize()
-    rows = torch.tensor([0, 1] if B == 2 else [0, 77] if B == 128 else [0, 201])
+    rows = torch.tensor(rows)
     x = x[rows]
     emb = emb[rows.to(DEV)].cpu()
     assert emb.dtype == torch.float32 and taps[0][0].dtype == torch.bfloat16

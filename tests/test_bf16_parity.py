@@ -62,9 +62,15 @@ def model(backbone, nb, st):
 
 
 def run(backbone, nb, B=64, rows=ROWS, st="bf16"):
-    key = (backbone, nb, B, st)
-    if key in _CACHE:
-        return _CACHE[key]
+    key = (backbone, nb, B, st, tuple(rows))
+    if key not in _CACHE:
+        _CACHE[key] = compute(backbone, nb, B, rows, st)
+    return _CACHE[key]
+
+
+def compute(backbone, nb, B, rows, st, fp32=True):
+    """One forward_taps of a batch of B on the GPU and the oracles' forwards of ``rows`` of it (not cached:
+    tests/test_batch_sweep.py walks many batch sizes).  fp32=False skips the fp32 oracle."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     p, G = model(backbone, nb, st)
@@ -84,9 +90,9 @@ def run(backbone, nb, B=64, rows=ROWS, st="bf16"):
     r = {"p": pe, "z": zr, "xt": xr, "Y": Y[ri].float().cpu(), "u8": u8[ri].cpu().numpy(),
          "attr": [a[ri].float().cpu() for a in attr], "blocks": [b[ri].float().cpu() for b in blocks]}
     r["emu"] = aei_ref.aei_forward_bf16_storage(pe, r["xt"], r["z"], backbone, nb, store=STORE[st])
-    r["fp32"], a32 = aei_ref.aei_forward(p, r["xt"], r["z"], backbone, nb)
-    r["fp32_attr"] = [a.float() for a in a32]
-    _CACHE[key] = r
+    if fp32:
+        r["fp32"], a32 = aei_ref.aei_forward(p, r["xt"], r["z"], backbone, nb)
+        r["fp32_attr"] = [a.float() for a in a32]
     return r
 
 
@@ -119,7 +125,10 @@ def check_blocks(r, backbone, nb, st="bf16"):
 def test_encoder_maps_match_emulation(backbone, nb, st):
     """The attribute encoder's eight maps (unet / linknet: conv4x4 + deconv4x4 chains) against the storage
     emulation."""
-    r = run(backbone, nb, st=st)
+    check_encoder_maps(run(backbone, nb, st=st), st)
+
+
+def check_encoder_maps(r, st="bf16"):
     for i, (g, e) in enumerate(zip(r["attr"], r["emu"][1]), 1):
         d = (g - e).abs()
         assert float(d.max()) <= 2 * ulp(float(e.abs().max()), st), (i, float(d.max()))
@@ -133,7 +142,10 @@ def test_resnet_encoder_maps_within_storage_error(st):
     (measured: outside the 2-ulp gate the conv4x4 chains pass): its maps are
     gated end to end like Y — per map, the GPU's error against the fp32 oracle within 1.25x (mean) / 1.3x (top
     0.5 %) of the emulated 16-bit arithmetic's own error."""
-    r = run("resnet", 2, 4, list(range(4)), st=st)
+    check_resnet_encoder_maps(run("resnet", 2, 4, list(range(4)), st=st), st)
+
+
+def check_resnet_encoder_maps(r, st="bf16"):
     for i, (g, e, f) in enumerate(zip(r["attr"], r["emu"][1], r["fp32_attr"]), 1):
         dg, de = (g - f).abs().flatten(), (e.float() - f).abs().flatten()
         tol = ulp(float(f.abs().max()), st) / 64

@@ -361,6 +361,152 @@ def test_conv3x3_splitk_residual_tanh(lib, split):
     assert float((got - ref).abs().max()) <= 1e-5
 
 
+# ----------------------------------------------------------------------------------------
+# edge classes of the implicit GEMM that no pipeline batch selects but the public conv entries accept: M and N
+# tails, ragged / one-step / clamped split-K, a last split shorter than the ring's prologue, both reduction
+# forms, the non-FAST gather with 16-bit operands.  Every case: bf16 and fp16, against a float64 conv of the
+# storage-rounded operands within 1.01 ulp of the storage type (test_conv3x3_64_op's gate), the output pre-filled
+# with NaN, ldy > Cout with a sentinel that must survive, and the plan log (ghost_plan_log) must show the intended
+# class.  The shapes were derived by hand from conv_igemm.hip make_plan; split_k > 0 keeps a conv off the halo and
+# patch kernels.  If a retuned heuristic moves a case to another variant, change the shape, not the class.
+# ----------------------------------------------------------------------------------------
+SENTINEL = 7.0
+
+
+def _logged_call(call):
+    """call() with the plan log on -> the signatures it launched, in order."""
+    from ghost_amd import _lib
+    _lib.plan_log(True)
+    try:
+        call()
+        torch.cuda.synchronize()
+    finally:
+        _lib.plan_log(False)
+    return _lib.plan_log_read()
+
+
+def _assert_plan(sigs, *wanted):
+    """Each of ``wanted`` (a tuple of tokens) must be matched by one logged signature holding all its tokens."""
+    for tokens in wanted:
+        assert any(all(t in s.split() for t in tokens) for s in sigs), (tokens, sigs)
+
+
+def _ulp_gate(got, ref, dt):
+    assert torch.isfinite(got).all()
+    ulp = 2.0 ** -7 if dt == torch.bfloat16 else 2.0 ** -10
+    d = (got.double() - ref).abs()
+    assert float((d / ref.abs().clamp_min(1.0)).max()) <= 1.01 * ulp, float(d.max())
+
+
+IGEMM_EDGES = [
+    # cin, ldx, cout, k, s, p, B, H, W, split_k, plan tokens (GEMM launch), reduction kernel
+    # glds 64x128, 3 stages, M = 120 (tail), non-square; nk = 27: splits 7,7,7,6 / one K step each / clamped to nk
+    (96, 96, 128, 3, 1, 1, 2, 6, 10, 4, ("glds", "64x128", "stages=3", "split=1", "ragged=1", "short=0", "mtail=1"),
+     "splitk_reduce4"),
+    (96, 96, 128, 3, 1, 1, 2, 6, 10, 27, ("glds", "64x128", "stages=3", "split=1", "ragged=0", "short=1", "mtail=1"),
+     "splitk_reduce4"),
+    (96, 96, 128, 3, 1, 1, 2, 6, 10, 100, ("glds", "64x128", "stages=3", "split=1", "ragged=0", "short=1", "mtail=1"),
+     "splitk_reduce4"),
+    # N tail: Cout 200 reduces four channels at a time, Cout 130 one
+    (64, 64, 200, 3, 1, 1, 3, 5, 7, 2, ("glds", "64x128", "split=1", "ntail=1", "mtail=1"), "splitk_reduce4"),
+    (64, 64, 130, 3, 1, 1, 3, 5, 7, 2, ("glds", "64x128", "split=1", "ntail=1", "mtail=1"), "splitk_reduce"),
+    # deep ring 128x128 x 8 stages; nk = 36: splits 8,8,8,8,4 (the last shorter than STAGES - 1) / one K step each
+    (128, 128, 256, 3, 1, 1, 2, 8, 8, 5, ("glds", "128x128", "stages=8", "split=1", "ragged=1", "lastshort=1",
+                                          "mtail=0"), "splitk_reduce4"),
+    (128, 128, 256, 3, 1, 1, 3, 5, 7, 5, ("glds", "128x128", "stages=8", "split=1", "ragged=1", "lastshort=1",
+                                          "mtail=1"), "splitk_reduce4"),
+    (128, 128, 256, 3, 1, 1, 2, 8, 8, 36, ("glds", "128x128", "stages=8", "split=1", "short=1", "mtail=0"),
+     "splitk_reduce4"),
+    (128, 128, 256, 3, 1, 1, 3, 5, 7, 36, ("glds", "128x128", "stages=8", "split=1", "short=1", "mtail=1"),
+     "splitk_reduce4"),
+    # the encoder's 4x4/s2 tile on the ring
+    (32, 32, 64, 4, 2, 1, 1, 12, 20, 2, ("glds", "128x64", "split=1", "mtail=1"), "splitk_reduce4"),
+    # register-staged kernel, 256x32 tile, 16-bit split
+    (64, 64, 24, 3, 1, 1, 2, 9, 5, 3, ("igemm", "256x32x32", "fast=1", "epi=SPLIT", "split=1", "ntail=1", "mtail=1"),
+     "splitk_reduce4"),
+    # 1x1/s2 (nk = 5): unsplit and one K step per split
+    (160, 160, 96, 1, 2, 0, 2, 10, 6, 0, ("glds", "64x128", "split=0", "ntail=1", "mtail=1"), None),
+    (160, 160, 96, 1, 2, 0, 2, 10, 6, 5, ("glds", "64x128", "split=1", "short=1", "ntail=1", "mtail=1"),
+     "splitk_reduce4"),
+    # the non-FAST gather (Cin % 32 != 0, padded input channels) with 16-bit operands
+    (20, 24, 70, 3, 1, 1, 2, 7, 6, 0, ("igemm", "64x64x32", "fast=0", "split=0", "ntail=1", "mtail=1"), None),
+]
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin,ldx,cout,k,s,p,B,H,W,split_k,plan,reduce", IGEMM_EDGES)
+def test_igemm_edge_plans(lib, dt, cin, ldx, cout, k, s, p, B, H, W, split_k, plan, reduce):
+    from ghost_amd import _lib
+    from ghost_amd.network.pack import pack_conv, rup
+    g = torch.Generator().manual_seed(cin * 31 + cout * 7 + H + split_k)
+    x = torch.randn(B, cin, H, W, generator=g)
+    w = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
+    sc = torch.rand(cout, generator=g) + 0.5
+    sh = torch.randn(cout, generator=g) * 0.1
+    xr, wr = x.to(dt).double(), w.to(dt).double()
+    ref = F.leaky_relu(F.conv2d(xr, wr, stride=s, padding=p) * sc.double().view(1, -1, 1, 1)
+                       + sh.double().view(1, -1, 1, 1), 0.2)
+    Ho, Wo = ref.shape[2:]
+    xin = torch.full((B, H, W, ldx), 7.0)     # padding channels must not contribute
+    xin[..., :cin] = x.permute(0, 2, 3, 1)
+    xd = xin.to(dt).to(DEV)
+    wp = pack_conv(w, dt).to(DEV)
+    ldy = cout + 8
+    y = torch.full((B, Ho, Wo, ldy), float("nan"), dtype=dt, device=DEV)
+    y[..., cout:] = SENTINEL
+    scp = torch.zeros(rup(cout, 128), device=DEV); scp[:cout] = sc.to(DEV)
+    shp = torch.zeros(rup(cout, 128), device=DEV); shp[:cout] = sh.to(DEV)
+    ws = torch.empty(64 << 20, dtype=torch.uint8, device=DEV)
+    e = _lib.ConvEpi()
+    e.scale, e.shift, e.slope, e.split_k = scp.data_ptr(), shp.data_ptr(), 0.2, split_k
+    sigs = _logged_call(lambda: _lib.check(lib.ghost_conv2d_ex_nhwc(
+        _lib.gdtype(dt), xd.data_ptr(), B, H, W, cin, ldx, wp.data_ptr(), cout, wp.shape[0], wp.shape[1], k, k, s, p,
+        C_byref(e), y.data_ptr(), ldy, ws.data_ptr(), ws.numel(), stream(lib))))
+    got = y.float().cpu()
+    assert torch.all(got[..., cout:] == SENTINEL), "wrote outside its channel slice"
+    _ulp_gate(got[..., :cout].permute(0, 3, 1, 2), ref, dt)
+    _assert_plan(sigs, plan + ("t=" + ("bf16" if dt == torch.bfloat16 else "f16"),) if plan[0] == "glds" else plan)
+    if reduce:
+        _assert_plan(sigs, (reduce,))
+    else:
+        assert not any(s_.startswith("splitk_reduce") for s_ in sigs), sigs
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cout,plan", [
+    (64, ("igemm", "256x64x32", "kind=T4S2", "split=1", "ragged=1", "mtail=1")),
+    (128, ("glds", "64x128", "kind=T4S2", "split=1", "ragged=1", "mtail=1")),
+])
+def test_convT_igemm_edge_plans(lib, dt, cout, plan):
+    """ConvT 4x4/s2 544 -> Cout at B = 1, 4 x 6 (M = 24 per parity class, nk = 68): the heuristic's 8 splits are
+    seven of 9 K steps and a last of 5.  The slice and sentinel layout of test_convT_op."""
+    from ghost_amd import _lib
+    from ghost_amd.network.pack import pack_convT4x4, rup
+    cin, H, W = 544, 4, 6
+    g = torch.Generator().manual_seed(cin + cout)
+    x = torch.randn(1, cin, H, W, generator=g)
+    w = torch.randn(cin, cout, 4, 4, generator=g) * (2.0 / (cin * 16)) ** 0.5
+    sc = torch.rand(cout, generator=g) + 0.5
+    sh = torch.randn(cout, generator=g) * 0.1
+    ref = F.leaky_relu(F.conv_transpose2d(x.to(dt).double(), w.to(dt).double(), stride=2, padding=1)
+                       * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1), 0.1)
+    wp = pack_convT4x4(w, dt).to(DEV)
+    ld = cout + 32
+    y = torch.full((1, 2 * H, 2 * W, ld), float("nan"), dtype=dt, device=DEV)
+    y[..., cout:] = SENTINEL
+    scp = torch.zeros(rup(cout, 128), device=DEV); scp[:cout] = sc.to(DEV)
+    shp = torch.zeros(rup(cout, 128), device=DEV); shp[:cout] = sh.to(DEV)
+    ws = torch.empty(64 << 20, dtype=torch.uint8, device=DEV)
+    xd = nhwc(x).to(dt).to(DEV)
+    sigs = _logged_call(lambda: _lib.check(lib.ghost_conv_transpose4x4s2_nhwc(
+        _lib.gdtype(dt), xd.data_ptr(), 1, H, W, cin, cin, wp.data_ptr(), cout, wp.shape[1], wp.shape[2],
+        scp.data_ptr(), shp.data_ptr(), 0.1, None, cout, y.data_ptr(), ld, ws.data_ptr(), ws.numel(), stream(lib))))
+    got = y.float().cpu()
+    assert torch.all(got[..., cout:] == SENTINEL), "wrote outside its channel slice"
+    _ulp_gate(got[..., :cout].permute(0, 3, 1, 2), ref, dt)
+    _assert_plan(sigs, plan, ("splitk_reduce4",))
+
+
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("B,C,H", [(2, 64, 256), (3, 1024, 2), (2, 256, 32), (1, 32, 5)])
 def test_instnorm_stats(lib, dt, B, C, H):

@@ -34,6 +34,17 @@ def test_library_exports_every_header_symbol(lib):
     assert set(declared) == set(_lib._SIGS), "ctypes signature table out of sync with include/ghost_amd.h"
 
 
+def test_plan_log_is_empty_without_launches_and_sizes_its_buffer(lib):
+    """ghost_plan_log / ghost_plan_log_read with no launch in between: an empty log needs one byte (the NUL), a
+    NULL buffer only asks for the size, and a short buffer is terminated inside its capacity."""
+    assert lib.ghost_plan_log(1) == 0
+    assert lib.ghost_plan_log_read(None, 0) == 1
+    buf = C.create_string_buffer(b"xxxx", 4)
+    assert lib.ghost_plan_log_read(buf, 4) == 1 and buf.raw[0:1] == b"\0" and buf.raw[1:] == b"xxx"
+    assert lib.ghost_plan_log(0) == 0
+    assert _lib.plan_log_read() == []
+
+
 @pytest.mark.parametrize("backbone,nb", [("unet", 2), ("linknet", 3), ("unet", 1), ("unet", 3), ("resnet", 2)])
 def test_pack_slots_match_runtime_plan(lib, backbone, nb):
     specs = aei_ref.param_specs(backbone, nb)
