@@ -71,6 +71,9 @@ _SIGS = {
     "ghost_roi_copy_u8": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, i32, i32, vp]),
     "ghost_align_crops_roi_u8": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i64, vp, i64, i32, vp]),
     "ghost_blend_swaps_roi_u8": (i32, [vp, i64, i32, i32, i32, vp, vp, i32, vp, i64, i32, i32, vp, i64, vp, vp, vp]),
+    "ghost_roi_packed_layout": (i32, [vp, i32, vp, i64p]),
+    "ghost_roi_pack_host": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32]),
+    "ghost_roi_unpack_u8": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, i64, i32, i32, i32, vp]),
     "ghost_mask_polygons": (i32, [vp, i32, i32, vp, vp, vp]),
     "ghost_face_masks_workspace_bytes": (i64, [i32, i32, i32]),
     "ghost_face_masks": (i32, [vp, vp, vp, i32, i32, i32, vp, i64, vp, i64, vp]),

@@ -6,3 +6,4 @@ from .faceshifter_run import faceshifter_batch, faceshifter_batch_u8  # noqa: F4
 from .graphed import GraphedSwap  # noqa: F401
 from .roi import (align_crops_roi, blend_swaps_roi, crop_frames_and_get_transforms_roi, download_rois,  # noqa: F401
                   face_rois, plan_rois, upload_rois)
+from .roi_pack import RoiStaging, download_rois_packed, packed_layout, upload_rois_packed  # noqa: F401

@@ -417,12 +417,17 @@ def _frame_hw(frames_host) -> Tuple[int, int]:
 
 def crop_frames_and_get_transforms_roi(frames_host, kps_per_frame: Sequence, target_embeds: torch.Tensor, netArc,
                                        crop_size: int, set_target: bool, similarity_th: float, templates, device,
-                                       embed_batch: int = 64):
+                                       embed_batch: int = 64, packed: bool = False):
     """``align.crop_frames_and_get_transforms`` with the frames on the host: the same bookkeeping and the same first
     four returns (crops, 256 x 256 crops, ``present``, ``tfm_array``, per identity), plus ``plan, patches`` for
     ``blend_swaps_roi`` / ``download_rois``.  The ArcFace matching of multi-face and ``set_target`` frames takes its
     crops from a temporary plan over the detector's unsmoothed transforms; the final crops come from the plan over
-    the smoothed ones, whose patches are returned."""
+    the smoothed ones, whose patches are returned.  ``packed=True`` uploads through ``roi_pack.upload_rois_packed``
+    (one copy per chunk of patches; the frames need not be pinned): the same returns, the same bytes."""
+    if packed:
+        from .roi_pack import upload_rois_packed as upload
+    else:
+        upload = upload_rois
     hw = _frame_hw(frames_host)
     dev = torch.device(device)
     if len(kps_per_frame) != len(frames_host):
@@ -444,7 +449,7 @@ def crop_frames_and_get_transforms_roi(frames_host, kps_per_frame: Sequence, tar
             for k, p in enumerate(kps_per_frame[i]):
                 det[k][i] = estimate_norm(p, crop_size, templates)[0]
         tmp = plan_rois(det, crop_size, hw)
-        tmp_patches = upload_rois(frames_host, tmp, dev)
+        tmp_patches = upload(frames_host, tmp, dev)
         faces = torch.empty(total, crop_size, crop_size, 3, dtype=torch.uint8, device=dev)
         for k in range(K):
             rows = tmp.frames_of(k)
@@ -460,7 +465,7 @@ def crop_frames_and_get_transforms_roi(frames_host, kps_per_frame: Sequence, tar
     kps_array = select_keypoints(kps_per_frame, T, set_target, matches)
     present, tfm_array = frame_transforms(kps_array, crop_size, templates)
     plan = plan_rois(tfm_array, crop_size, hw)
-    patches = upload_rois(frames_host, plan, dev)
+    patches = upload(frames_host, plan, dev)
     crop_frames, resized_frames = [], []
     for q in range(T):
         c, r = align_crops_roi(patches, plan, q, plan.tfms[q, plan.frames_of(q)], crop_size, resize_to=256)

@@ -349,6 +349,41 @@ int ghost_blend_swaps_roi_u8(uint8_t* patches, int64_t patch_stride, int Np, int
                              int Ws, const float* masks, int64_t mask_stride, const float* mats, const int32_t* valid,
                              void* stream);
 
+/* ---- packed ROI transfer: one host-link copy per chunk of patches, not one per rectangle ----
+ * The per-patch copies of ghost_roi_copy_u8 run at 5-11 GB/s and need pinned frames to be asynchronous.  Here the
+ * rectangles of a plan are packed into one buffer: rectangle p = (x0, y0, w, h) occupies h rows of pitch
+ * pitch_p = (3 w + 15) & ~15 bytes from byte offset_p, offset_0 = 0, offset_{p+1} = offset_p + pitch_p h_p rounded up
+ * to a multiple of 256; an empty rectangle (w or h 0) takes no bytes; total = the offset after the last rectangle.
+ * Offsets ascend in patch order, so the patches [p0, p1) are one contiguous byte range (one hipMemcpyAsync moves the
+ * chunk), and every packed row starts 16-byte aligned.
+ * ghost_roi_packed_layout (host only) writes offsets_host [Np] and *total_bytes for rects_host int32 [Np][4]; a
+ * negative w or h is GHOST_EINVAL; Np == 0 gives total 0.
+ * ghost_roi_pack_host (host only, no device pointer) copies the 3 w bytes of every row of every rectangle in [p0, p1)
+ * between frame_ptrs_host[p] + (y0 W + x0) 3 (pitch 3 W; indexed by patch as for ghost_roi_copy_u8, any host memory)
+ * and staging + offset_p (pitch pitch_p): into the staging buffer with to_staging != 0, back otherwise.  Row padding
+ * and the gaps between rectangles are never written; on the way back exactly the rectangles' bytes of a frame are.
+ * Before the first byte moves every rectangle of the range is checked: inside the H x W frame, a non-null frame,
+ * offset_p >= 0 and a multiple of 16, offset_p + pitch_p h_p <= staging_bytes and <= offset_{p+1} (GHOST_EINVAL,
+ * nothing copied).  Empty rectangles are skipped; p0 == p1 returns GHOST_OK.  The rows are split by bytes, not by
+ * patch, over `threads` worker threads (0 = 8, clamped to 1..16; a short range uses fewer) that are joined before the
+ * call returns; the result does not depend on threads.  Back into the frames, two rectangles of one frame that
+ * overlap are the caller's error (plan_rois' merge rule makes them disjoint).
+ * ghost_roi_unpack_u8 (device; rects, offsets, packed are device arrays, packed 16-byte aligned) copies the packed
+ * rows of the patches [p0, p1) into the canvas of the ROI block above with to_canvas != 0 and the canvas rectangles
+ * into the packed rows otherwise.  w and h are clamped to the canvas (the packed pitch stays that of the plan's w); a
+ * patch whose offset is negative, not a multiple of 16, or whose offset + pitch h exceeds packed_bytes is skipped
+ * before any access.  Toward the canvas only the rectangle's bytes are written; toward the packed buffer a row may be
+ * written up to its pitch (padding content unspecified) and nothing past offset + pitch h; no canvas access leaves
+ * the patch's Ph Pw 3 bytes.  p1 - p0 <= 65535; a null pointer or a bad canvas is GHOST_EINVAL; p0 == p1 returns
+ * GHOST_OK without a launch.  No call allocates or synchronises. */
+int ghost_roi_packed_layout(const int32_t* rects_host, int Np, int64_t* offsets_host, int64_t* total_bytes);
+int ghost_roi_pack_host(uint8_t* staging, int64_t staging_bytes, const int32_t* rects_host,
+                        const int64_t* offsets_host, uint8_t* const* frame_ptrs_host, int Np, int p0, int p1, int H,
+                        int W, int to_staging, int threads);
+int ghost_roi_unpack_u8(uint8_t* patches, int64_t patch_stride, int Np, int Ph, int Pw, const int32_t* rects,
+                        const int64_t* offsets, uint8_t* packed, int64_t packed_bytes, int p0, int p1, int to_canvas,
+                        void* stream);
+
 /* ---- face masks (face_mask_static, utils/inference/masks.py:38-107) ----
  * Host, CPU only (no device pointers): for F frames of 106 float32 landmarks [F][106][2] and their
  * (erode, sigmaX, sigmaY) params [F][3] (face_mask_static's, masks.py:43-65), expand_eyebrows on the int32
