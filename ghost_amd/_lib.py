@@ -95,6 +95,10 @@ _SIGS = {
     "ghost_aad_layers_v3_nhwc": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp),
                                        C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, f32, C.POINTER(vp),
                                        C.POINTER(i32), vp, i64, vp]),
+    "ghost_aad_layers_v3_dt_nhwc": (i32, [i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp),
+                                          C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, f32,
+                                          C.POINTER(vp), C.POINTER(i32), vp, i64, vp]),
+    "ghost_aad_mask_nhwc": (i32, [i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "ghost_conv3x3_narrow_nhwc": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, i32, vp,
                                         vp]),
     "ghost_plan_log": (i32, [i32]),

@@ -1538,11 +1538,11 @@ extern "C" int ghost_conv3x3_narrow_nhwc(int dtype, const void* x, int B, int H,
   return rc ? fail(rc, "conv3x3_narrow failed (H % 8, W % 32, Cin % 32 and Cout <= 3 required)") : 0;
 }
 
-extern "C" int ghost_aad_layers_v3_nhwc(const void* h_in, int ldh, int up2x, const void* z_attr, int lda, int B, int H,
-                                        int W, int C, int Ca, int L, const void* const w3[], const float* const b3[],
-                                        const float* const wh[], const float* const bh[], const float* const idgb[],
-                                        int id_ld, float slope, void* const out[], const int ldo[], void* ws,
-                                        int64_t ws_bytes, void* stream) {
+extern "C" int ghost_aad_layers_v3_dt_nhwc(int dtype, const void* h_in, int ldh, int up2x, const void* z_attr, int lda,
+                                           int B, int H, int W, int C, int Ca, int L, const void* const w3[],
+                                           const float* const b3[], const float* const wh[], const float* const bh[],
+                                           const float* const idgb[], int id_ld, float slope, void* const out[],
+                                           const int ldo[], void* ws, int64_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int HW = H * W;
   if (L < 1 || L > 2) return fail(GHOST_EINVAL, "aad_v3: L must be 1 or 2");
@@ -1550,27 +1550,28 @@ extern "C" int ghost_aad_layers_v3_nhwc(const void* h_in, int ldh, int up2x, con
   if (up2x && (H % 2 || W % 2 || (C != 64 && C != 128)))
     return fail(GHOST_EINVAL, "aad_v3: up2x needs even H, W and C in {64, 128}");
   // aad_wide: one layer, C in {256, 512, 1024}, Ca <= 512, where the all-channel kernel does not fit
-  const bool wide = C >= 256 && !aad_v3_supported(GHOST_BF16, B, HW, C, Ca, lda, ldh, ldo[0]);
-  if (wide && (L != 1 || up2x || !aad_wide_supported(GHOST_BF16, B, HW, C, Ca, lda, ldh, ldo[0])))
+  const bool wide = C >= 256 && !aad_v3_supported(dtype, B, HW, C, Ca, lda, ldh, ldo[0]);
+  if (wide && (L != 1 || up2x || !aad_wide_supported(dtype, B, HW, C, Ca, lda, ldh, ldo[0])))
     return fail(GHOST_EINVAL, "aad_wide: unsupported shape (one layer, C in {256,512,1024}, Ca <= 512)");
   for (int l = 0; l < L && !wide; ++l)
-    if (!aad_v3_supported(GHOST_BF16, B, HW, C, Ca, lda, ldh, ldo[l]))
-      return fail(GHOST_EINVAL, "aad_v3: unsupported shape (bf16, C in {64,128}, enough pixels)");
+    if (!aad_v3_supported(dtype, B, HW, C, Ca, lda, ldh, ldo[l]))
+      return fail(GHOST_EINVAL, "aad_v3: unsupported shape (bf16 / fp16, C in {64,128}, enough pixels)");
   const size_t stat_b = ((size_t)B * C * 2 * sizeof(float) + 255) & ~size_t(255);
   const size_t sc = in_stats_workspace_bytes(B, HW, C);
   char* base = (char*)(((uintptr_t)ws + 255) & ~uintptr_t(255));
   if (!ws || (size_t)ws_bytes < stat_b + sc + 256) return fail(GHOST_ENOWS, "aad_v3: workspace too small");
   float* stat = (float*)base;
-  int rc = up2x ? in_stats_up2x(GHOST_BF16, h_in, ldh, B, H / 2, W / 2, C, stat, base + stat_b, sc, s)
-                : in_stats(GHOST_BF16, h_in, ldh, B, HW, C, stat, base + stat_b, sc, s);
+  int rc = up2x ? in_stats_up2x(dtype, h_in, ldh, B, H / 2, W / 2, C, stat, base + stat_b, sc, s)
+                : in_stats(dtype, h_in, ldh, B, HW, C, stat, base + stat_b, sc, s);
   if (rc) return fail(rc, "aad_v3: in_stats failed");
   if (wide) {
     const size_t mask_b = ((size_t)B * HW * sizeof(float) + 255) & ~size_t(255);
     if ((size_t)ws_bytes < stat_b + sc + mask_b + 256) return fail(GHOST_ENOWS, "aad_wide: workspace too small");
     float* mask = (float*)(base + stat_b + sc);
-    rc = aad_mask(GHOST_BF16, h_in, ldh, B, HW, C, stat, wh[0], bh[0], mask, s);
+    rc = aad_mask(dtype, h_in, ldh, B, HW, C, stat, wh[0], bh[0], mask, s);
     if (rc) return fail(rc, "aad_wide: aad_mask failed");
     AadWideDesc w;
+    w.dt = dtype;
     w.mask = mask;
     w.za = z_attr; w.lda = lda; w.Ca = Ca; w.hin = h_in; w.ldh = ldh; w.stat = stat;
     w.B = B; w.HW = HW; w.C = C; w.id_ld = id_ld; w.slope = slope;
@@ -1579,6 +1580,7 @@ extern "C" int ghost_aad_layers_v3_nhwc(const void* h_in, int ldh, int up2x, con
     return rc ? fail(rc, "aad_wide launch failed") : 0;
   }
   AadV3Desc d;
+  d.dt = dtype;
   d.za = z_attr; d.lda = lda; d.Ca = Ca; d.hin = h_in; d.ldh = ldh; d.stat = stat;
   d.B = B; d.HW = HW; d.C = C; d.L = L; d.id_ld = id_ld; d.slope = slope;
   if (up2x) {
@@ -1591,4 +1593,29 @@ extern "C" int ghost_aad_layers_v3_nhwc(const void* h_in, int ldh, int up2x, con
   }
   rc = aad_v3(d, s);
   return rc ? fail(rc, "aad_v3 launch failed") : 0;
+}
+
+extern "C" int ghost_aad_layers_v3_nhwc(const void* h_in, int ldh, int up2x, const void* z_attr, int lda, int B, int H,
+                                        int W, int C, int Ca, int L, const void* const w3[], const float* const b3[],
+                                        const float* const wh[], const float* const bh[], const float* const idgb[],
+                                        int id_ld, float slope, void* const out[], const int ldo[], void* ws,
+                                        int64_t ws_bytes, void* stream) {
+  return ghost_aad_layers_v3_dt_nhwc(GHOST_BF16, h_in, ldh, up2x, z_attr, lda, B, H, W, C, Ca, L, w3, b3, wh, bh, idgb,
+                                     id_ld, slope, out, ldo, ws, ws_bytes, stream);
+}
+
+extern "C" int ghost_aad_mask_nhwc(int dtype, const void* h, int ldh, int B, int HW, int C, float* stat, const float* wh0,
+                                   const float* bh0, float* mask0, const float* wh1, const float* bh1, float* mask1,
+                                   int small, void* stream) {
+  if (!h || !stat || !wh0 || !bh0 || !mask0 || (wh1 && (!bh1 || !mask1)))
+    return fail(GHOST_EINVAL, "aad_mask: null argument");
+  if (B < 1 || HW < 1 || C < 1) return fail(GHOST_EINVAL, "aad_mask: empty shape");
+  if (small) {
+    if (!stats_mask_small_ok(dtype, HW, C, ldh))
+      return fail(GHOST_EINVAL, "aad_mask: small form needs HW <= 16, C <= 1024, C and ldh multiples of the vector");
+    int rc = stats_mask_small(dtype, h, ldh, B, HW, C, stat, wh0, bh0, mask0, wh1, bh1, mask1, (hipStream_t)stream);
+    return rc ? fail(rc, "stats_mask_small failed") : 0;
+  }
+  int rc = aad_mask2(dtype, h, ldh, B, HW, C, stat, wh0, bh0, mask0, wh1, bh1, mask1, (hipStream_t)stream);
+  return rc ? fail(rc, "aad_mask2 failed") : 0;
 }

@@ -240,6 +240,20 @@ int ghost_aad_layers_v3_nhwc(const void* h_in, int ldh, int up2x, const void* z_
                              const float* const wh[], const float* const bh[], const float* const idgb[], int id_ld,
                              float slope, void* const out[], const int ldo[], void* ws, int64_t ws_bytes,
                              void* stream);
+/* Test support: ghost_aad_layers_v3_nhwc with the 16-bit storage type (GHOST_BF16 or GHOST_F16) as an argument;
+ * ghost_aad_layers_v3_nhwc is this with GHOST_BF16. */
+int ghost_aad_layers_v3_dt_nhwc(int dtype, const void* h_in, int ldh, int up2x, const void* z_attr, int lda, int B,
+                                int H, int W, int C, int Ca, int L, const void* const w3[], const float* const b3[],
+                                const float* const wh[], const float* const bh[], const float* const idgb[],
+                                int id_ld, float slope, void* const out[], const int ldo[], void* ws, int64_t ws_bytes,
+                                void* stream);
+/* Test support: the AAD mask kernels alone.  mask_l[b*HW + p] = sigmoid(sum_c wh_l[c] (h[p,c] - mean[b,c]) rstd[b,c]
+ * + bh_l) in fp32 for one (wh1 == NULL) or two layers reading the same h [B, HW, C] (ldh).  small = 0: stat
+ * ([B][C][2] mean, rstd) is an input; small = 1: the one-launch statistics + mask kernel of the HW <= 16 stages,
+ * which also writes stat (GHOST_EINVAL unless HW <= 16 and C <= 1024). */
+int ghost_aad_mask_nhwc(int dtype, const void* h, int ldh, int B, int HW, int C, float* stat, const float* wh0,
+                        const float* bh0, float* mask0, const float* wh1, const float* bh1, float* mask1, int small,
+                        void* stream);
 int ghost_upsample2x_nhwc(int dtype, const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C,
                           void* stream);
 int ghost_nhwc_to_nchw(int dtype, const void* x, int ldx, int B, int H, int W, int C, void* y, void* stream);
