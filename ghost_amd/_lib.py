@@ -103,6 +103,7 @@ _SIGS = {
                                         vp]),
     "ghost_plan_log": (i32, [i32]),
     "ghost_plan_log_read": (i64, [C.c_char_p, i64]),
+    "ghost_aad_plan": (i64, [i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, C.POINTER(i32), C.c_char_p, i64]),
 }
 
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "plan_log.h"
+
 namespace ghost {
 
 struct AadV3Desc {
@@ -29,19 +31,35 @@ struct AadV3Desc {
   // zr_image(HW) fp16 per sample, and the image width must be a multiple of 8
   const void* zw[2] = {nullptr, nullptr};
   int zwld = 0;
-  // in-kernel clock of the launch (profiling; v4 / v5): aad_v3_clock_words(d) words of per-workgroup start
+  // in-kernel clock of the launch (profiling; v4 / v5): AadV3Plan::clock_words words of per-workgroup start
   // and per-wave end stamps
   unsigned long long* tclk = nullptr;
-  int* version_out = nullptr;   // set to the kernel generation that ran (3, 4 or 5)
 };
+
+// What a launch of a descriptor runs, decided from its integers and flags alone (dt, B, HW, C, Ca, L, the leading
+// dimensions, up_H / up_W, zwld, slope == 0, which zw[l] are set): no pointer is read through, no HIP call made.
+enum class AadV3Kernel { None, V3, V3Wide, V3Zp1, V3Z, V4, V4Z, V5, V5Z, V5ZAsm, V5Wide };
+struct AadV3Plan {
+  AadV3Kernel kernel = AadV3Kernel::None;   // None: no kernel takes this descriptor
+  int version = 0;                          // kernel generation: 3, 4 or 5
+  int ppw = 0, ipw = 0, zpm = 0;            // pixels per workgroup / work item, v5 work items per workgroup, zw mask
+  unsigned grid = 0, block = 0, dyn_lds = 0;
+  int clock_words = 0;                      // words a launch with tclk set stamps (0: generation 3 stamps none)
+};
+AadV3Plan aad_v3_plan(const AadV3Desc& d);
+PlanSig aad_v3_signature(const AadV3Plan& p, const AadV3Desc& d);   // the plan-log line of (plan, desc)
 
 // the 3x3 / pad 1 conv to 3 channels from two tap-partial buffers (AADBlk8's output conv over
 // cat(h, x'), AADLayer.py:71,79): y = tanh(sum_t (zh + zx)[p + off_t][t*3 + o]) -> bf16 y (ldy) + BGR uint8
 int tap_sum3x3(int dt, const void* zh, const void* zx, int B, int H, int W, void* y, int ldy, uint8_t* u8,
                hipStream_t s);
 
-int aad_v3_clock_words(const AadV3Desc& d);
+// the (C, Ca) with a kernel here, and how many AADLayers one launch of it blends (1 or 2; 0: none)
+int aad_v3_max_layers(int C, int Ca);
+// true when a one-layer launch of this shape has a plan
 bool aad_v3_supported(int dt, int B, int HW, int C, int Ca, int lda, int ldh, int ldo);
+// launches p = aad_v3_plan(d) (the second form plans itself); -1 when the plan is None or a zw[l] is misaligned
+int aad_v3(const AadV3Desc& d, const AadV3Plan& p, hipStream_t s);
 int aad_v3(const AadV3Desc& d, hipStream_t s);
 
 }  // namespace ghost

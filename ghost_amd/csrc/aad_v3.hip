@@ -16,6 +16,7 @@
 // beta of 16 *contiguous-in-pairs-of-8* channels of ONE pixel: the blend needs no LDS
 // round trip and every global access is a 16-byte vector along channels.
 // HBM bytes per launch = |h_in| + |z_attr| + L * |out|  (the algorithmic minimum).
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -1190,6 +1191,10 @@ static bool v5_pairing_ok(const Up2xSrc& u) {
   return true;
 }
 
+// ---------------------------------------------------------------------------------------------
+// host side: aad_v3_plan decides (kernel, grid, block, LDS, work split) from the descriptor's integers; aad_v3
+// fills the arguments and launches the plan's kernel from the one table of instantiations
+// ---------------------------------------------------------------------------------------------
 // pixels per workgroup: one sample's block; C = 256 stages its weights once per 1024 pixels, and so may the
 // C = 128 layers (128 x 128 stage: GHOST_V3_PPW128, A/B knob)
 // B > 0: a small batch halves the C = 128 / 256 workgroups (down to 256 pixels, a multiple of the 8 waves' 16-pixel
@@ -1205,7 +1210,7 @@ static int v3_ppw(int HW, int C, long B = 0) {
   return ppw;
 }
 
-// the v5 kernel's work items per workgroup if it takes this launch, else 0
+// the v5 kernels' work items per workgroup if they take this launch (one aad_v3_plan found valid), else 0
 static int v5_takes(const AadV3Desc& d, int zpm) {
   static const int use_v5 = GHOST_KNOB("GHOST_AAD_V5", 1);
   // two 1024-pixel work items per workgroup (one prologue — statistics tables, weight rows — per 2048 pixels):
@@ -1233,198 +1238,181 @@ static int v5_takes(const AadV3Desc& d, int zpm) {
     return 0;
   }
   if (d.C != 64 || v3_ppw(d.HW, d.C) != 1024 || ipw < 1 || d.up_H % rt || (d.up_H / rt) % ipw) return 0;
-  if (!(d.Ca == 64 || d.Ca == 32) || (zpm && d.L != 2) || ipw > 2) return 0;   // the kernel holds <= 2 row tiles
+  if ((zpm && d.L != 2) || ipw > 2) return 0;   // the kernel holds <= 2 row tiles
   // one work item per workgroup where two would leave the grid under a round of workgroups (B = 1: 32 -> 64)
   return (long)d.B * d.HW / 1024 / ipw >= 256 ? ipw : 1;
 }
 
-int aad_v3_clock_words(const AadV3Desc& d) {
-  long grid = (long)d.B * d.HW / v3_ppw(d.HW, d.C, d.B);
-  int zpm = 0;
-  for (int l = 0; l < d.L; ++l) zpm |= d.zw[l] ? 1 << l : 0;
-  if (const int ipw = v5_takes(d, zpm)) grid = (long)d.B * d.HW / 1024 / ipw;
-  return (int)(grid * (1 + kWaves));
-}
-
-bool aad_v3_supported(int dt, int B, int HW, int C, int Ca, int lda, int ldh, int ldo) {
-  if (!is16(dt)) return false;
+int aad_v3_max_layers(int C, int Ca) {
   // C = 256 (the 64x64 stage): all four channel tiles' weight rows (139 KB at Ca = 128) resident, one
   // workgroup per CU; the mask is computed in-kernel from the pixel's 256 channels, so no separate
   // mask pass reads h_in (measured B = 64: the per-channel-tile aad_wide + mask pass took 92 + 25 us)
   static const int c256 = GHOST_KNOB("GHOST_AAD_V3_C256", 1);
-  const bool shape = (C == 64 && (Ca == 64 || Ca == 32)) || (C == 128 && (Ca == 128 || Ca == 64 || Ca == 32)) ||
-                     (c256 && C == 256 && (Ca == 128 || Ca == 64));
-  if (!shape || lda % 8 || ldh % 8 || ldo % 8) return false;
-  const int ppw = v3_ppw(HW, C, B);
-  return HW % ppw == 0 && (long)B * HW / ppw >= 32;
+  if (C == 64 && (Ca == 64 || Ca == 32)) return 2;
+  if (C == 128 && (Ca == 128 || Ca == 64 || Ca == 32)) return Ca == 64 ? 2 : 1;   // the AADBlk7 block-input pair
+  return c256 && C == 256 && (Ca == 128 || Ca == 64) ? 1 : 0;
+}
+
+AadV3Plan aad_v3_plan(const AadV3Desc& d) {
+  typedef AadV3Kernel K;
+  AadV3Plan p;
+  const bool up = d.up_H > 0;
+  if (!is16(d.dt) || d.L < 1 || d.L > aad_v3_max_layers(d.C, d.Ca) || d.lda % 8 || d.ldh % 8) return p;
+  int zpm = 0;
+  for (int l = 0; l < d.L; ++l) {
+    if (d.ldo[l] % 8) return p;
+    zpm |= d.zw[l] ? 1 << l : 0;
+  }
+  if (zpm && (d.C != 64 || d.slope != 0.f || d.zwld % 8)) return p;
+  if (up && (4 * d.up_H * d.up_W != d.HW || d.up_W * 2 < 16 || (d.C != 64 && d.C != 128))) return p;
+  int ppw = v3_ppw(d.HW, d.C, d.B);
+  if (d.HW % ppw || (long)d.B * d.HW / ppw < 32) return p;
+  // v4 (prefetching) only for the through-upsample form: measured B = 64, 256x256 L = 2: 724 vs 734 us
+  // with the upsample, 604 vs 550 us without it (there v3's register loads win)
+  static const int use_v4 = GHOST_KNOB("GHOST_AAD_V4", 1);
+  static const unsigned dyn_lds = GHOST_KNOB("GHOST_AAD_DYNLDS", 0u);
+  static const int v5_asm = GHOST_KNOB("GHOST_V5_ASM", 1);
+  const int ipw = v5_takes(d, zpm);
+  K k;
+  if (ipw) {
+    k = d.C == 128 ? K::V5Wide : !zpm ? K::V5 : v5_asm ? K::V5ZAsm : K::V5Z;
+    ppw = 1024;   // the v5 work item
+  } else if (d.dt == GHOST_BF16 && use_v4 && up && d.C == 64 && ppw % 256 == 0 && (!zpm || d.L == 2)) {
+    k = zpm ? K::V4Z : K::V4;   // v4z: AADBlk8's block-input pair with tap partials in layer 1 (nb >= 2) or both
+  } else if (zpm) {   // the non-upsampled forms with tap partials (AADBlk8's last add_block; fuse_upsample off)
+    if (up) return p;
+    k = d.L == 1 ? K::V3Zp1 : K::V3Z;
+  } else {
+    k = d.C == 64 ? K::V3 : K::V3Wide;
+  }
+  p.kernel = k;
+  p.version = ipw ? 5 : (k == K::V4 || k == K::V4Z) ? 4 : 3;
+  p.ppw = ppw; p.ipw = ipw; p.zpm = zpm;
+  p.grid = (unsigned)((long)d.B * d.HW / ppw / (ipw ? ipw : 1));
+  p.block = k == K::V5Wide ? 1024 : kWaves * 64;
+  p.dyn_lds = k == K::V4 ? dyn_lds : 0;
+  // the kernels that stamp a.tclk: v4 and the C = 64 v5 forms
+  p.clock_words = p.version >= 4 && k != K::V5Wide ? (int)(p.grid * (1 + kWaves)) : 0;
+  return p;
+}
+
+bool aad_v3_supported(int dt, int B, int HW, int C, int Ca, int lda, int ldh, int ldo) {
+  AadV3Desc d;
+  d.dt = dt; d.B = B; d.HW = HW; d.C = C; d.Ca = Ca; d.lda = lda; d.ldh = ldh; d.ldo[0] = ldo;
+  return aad_v3_plan(d).kernel != AadV3Kernel::None;
+}
+
+PlanSig aad_v3_signature(const AadV3Plan& p, const AadV3Desc& d) {
+  static const char* const names[] = {"none",   "aad_v3", "aad_v3_wide", "aad_v3_zp1",  "aad_v3z",    "aad_v4",
+                                      "aad_v4z", "aad_v5", "aad_v5z",     "aad_v5z_asm", "aad_v5_wide"};
+  PlanSig g;
+  snprintf(g.s, sizeof(g.s), "%s t=%s C=%d Ca=%d L=%d up=%d zpm=%d slope0=%d v5_ipw=%d ppw=%d", names[(int)p.kernel],
+           plan_dt(d.dt), d.C, d.Ca, d.L, (int)(d.up_H > 0), p.zpm, d.slope == 0.f, p.ipw, p.ppw);
+  return g;
+}
+
+// every instantiation, once: (kernel, C, Ca, L, up, relu, zpm) -> the kernel; relu -1: the kernel reads a.slope
+template <typename T>
+using AadV3Fn = void (*)(const AadV3ArgsT<T>);
+template <typename T>
+struct AadV3Row {
+  AadV3Kernel kernel;
+  int C, Ca, L, up, relu, zpm;
+  AadV3Fn<T> fn;
+};
+
+template <typename T>
+static AadV3Fn<T> aad_v3_fn(const AadV3Plan& p, const AadV3Desc& d) {
+  auto find = [&](const AadV3Row<T>* r, size_t n) -> AadV3Fn<T> {
+    for (size_t i = 0; i < n; ++i)
+      if (r[i].kernel == p.kernel && r[i].C == d.C && r[i].Ca == d.Ca && r[i].L == d.L && r[i].up == (d.up_H > 0) &&
+          (r[i].relu < 0 || r[i].relu == (d.slope == 0.f)) && r[i].zpm == p.zpm)
+        return r[i].fn;
+    return nullptr;
+  };
+#define GHOST_ROW(k, c, ca, l, u, relu, zm, ...) {AadV3Kernel::k, c, ca, l, u, relu, zm, __VA_ARGS__},
+#define GHOST_V3(c, ca, l, u) GHOST_ROW(V3, c, ca, l, u, -1, 0, aad_v3_kernel<T, c, ca, l, u>)
+#define GHOST_V3W(c, ca, l, u) GHOST_ROW(V3Wide, c, ca, l, u, -1, 0, aad_v3_wide_kernel<T, c, ca, l, u>)
+#define GHOST_V3Z(ca, zm) GHOST_ROW(V3Z, 64, ca, 2, false, -1, zm, aad_v3_kernel<T, 64, ca, 2, false, zm>)
+#define GHOST_V5(ca, l)                                                                \
+  GHOST_ROW(V5, 64, ca, l, true, 1, 0, aad_v5_kernel<T, ca, l, true, 0, false>)         \
+  GHOST_ROW(V5, 64, ca, l, true, 0, 0, aad_v5_kernel<T, ca, l, false, 0, false>)
+#define GHOST_V5Z(ca, zm)                                                              \
+  GHOST_ROW(V5ZAsm, 64, ca, 2, true, 1, zm, aad_v5_kernel<T, ca, 2, true, zm, true>)    \
+  GHOST_ROW(V5Z, 64, ca, 2, true, 1, zm, aad_v5_kernel<T, ca, 2, true, zm, false>)
+#define GHOST_V5W(l)                                                                   \
+  GHOST_ROW(V5Wide, 128, 64, l, true, 1, 0, aad_v5_wide_kernel<T, 64, l, true>)         \
+  GHOST_ROW(V5Wide, 128, 64, l, true, 0, 0, aad_v5_wide_kernel<T, 64, l, false>)
+  static const AadV3Row<T> rows[] = {
+      GHOST_V3(64, 64, 1, false) GHOST_V3(64, 64, 2, false) GHOST_V3(64, 32, 1, false) GHOST_V3(64, 32, 2, false)
+      // through-upsample forms: the block-input AADLayers of AADBlk8 (first add_block + last_add_block)
+      GHOST_V3(64, 64, 2, true) GHOST_V3(64, 32, 2, true) GHOST_V3(64, 64, 1, true) GHOST_V3(64, 32, 1, true)
+      GHOST_V3W(128, 128, 1, false) GHOST_V3W(128, 64, 1, false) GHOST_V3W(128, 32, 1, false)
+      // the AADBlk7 block-input pair (C = 128, Ca = 64): one pass over h_in / z_attr for both layers, h_in
+      // materialised or (UP) sampled from the 64x64 AADBlk6 output on the fly
+      GHOST_V3W(128, 64, 2, false) GHOST_V3W(128, 64, 2, true)
+      // AADBlk7's block-input AADLayers read upsample2x(AADBlk6 output) on the fly (C = 128)
+      GHOST_V3W(128, 128, 1, true) GHOST_V3W(128, 64, 1, true) GHOST_V3W(128, 32, 1, true)
+      GHOST_V3W(256, 128, 1, false) GHOST_V3W(256, 64, 1, false)
+      GHOST_ROW(V3Zp1, 64, 64, 1, false, -1, 1, aad_v3_zp1_kernel<T, 64>)
+      GHOST_ROW(V3Zp1, 64, 32, 1, false, -1, 1, aad_v3_zp1_kernel<T, 32>)
+      GHOST_V3Z(64, 1) GHOST_V3Z(32, 1) GHOST_V3Z(64, 2) GHOST_V3Z(32, 2) GHOST_V3Z(64, 3) GHOST_V3Z(32, 3)
+      GHOST_V5(64, 1) GHOST_V5(64, 2) GHOST_V5(32, 1) GHOST_V5(32, 2)
+      GHOST_V5Z(64, 1) GHOST_V5Z(64, 2) GHOST_V5Z(64, 3) GHOST_V5Z(32, 1) GHOST_V5Z(32, 2) GHOST_V5Z(32, 3)
+      GHOST_V5W(1) GHOST_V5W(2)};
+  if (const AadV3Fn<T> fn = find(rows, sizeof(rows) / sizeof(rows[0]))) return fn;
+  if constexpr (std::is_same<T, bf16>::value) {   // v4 is bf16 only
+#define GHOST_V4(ca, l)                                                                \
+  GHOST_ROW(V4, 64, ca, l, true, 1, 0, aad_v4_kernel<ca, l, true, true>)                \
+  GHOST_ROW(V4, 64, ca, l, true, 0, 0, aad_v4_kernel<ca, l, true, false>)
+#define GHOST_V4Z(ca, zm) GHOST_ROW(V4Z, 64, ca, 2, true, 1, zm, aad_v4_kernel<ca, 2, true, true, zm>)
+    static const AadV3Row<bf16> rows_v4[] = {
+        GHOST_V4(64, 1) GHOST_V4(64, 2) GHOST_V4(32, 1) GHOST_V4(32, 2)
+        GHOST_V4Z(64, 1) GHOST_V4Z(64, 2) GHOST_V4Z(64, 3) GHOST_V4Z(32, 1) GHOST_V4Z(32, 2) GHOST_V4Z(32, 3)};
+    return find(rows_v4, sizeof(rows_v4) / sizeof(rows_v4[0]));
+#undef GHOST_V4Z
+#undef GHOST_V4
+  }
+  return nullptr;
+#undef GHOST_V5W
+#undef GHOST_V5Z
+#undef GHOST_V5
+#undef GHOST_V3Z
+#undef GHOST_V3W
+#undef GHOST_V3
+#undef GHOST_ROW
 }
 
 template <typename T>
-static int aad_v3_t(const AadV3Desc& d, hipStream_t s) {
+static int aad_v3_t(const AadV3Desc& d, const AadV3Plan& p, hipStream_t s) {
+  const AadV3Fn<T> fn = aad_v3_fn<T>(p, d);
+  if (!fn) return -1;
   AadV3ArgsT<T> a{};
   a.za = (const T*)d.za; a.hin = (const T*)d.hin; a.stat = d.stat;
   for (int l = 0; l < d.L; ++l) {
     a.w3[l] = (const T*)d.w3[l]; a.b3[l] = d.b3[l]; a.wh[l] = d.wh[l]; a.bh[l] = d.bh[l];
-    a.idgb[l] = d.idgb[l]; a.out[l] = (T*)d.out[l]; a.ldo[l] = d.ldo[l];
+    a.idgb[l] = d.idgb[l]; a.out[l] = (T*)d.out[l]; a.ldo[l] = d.ldo[l]; a.zw[l] = (const T*)d.zw[l];
   }
-  a.lda = d.lda; a.ldh = d.ldh; a.id_ld = d.id_ld; a.HW = d.HW; a.slope = d.slope;
-  a.PPW = v3_ppw(d.HW, d.C, d.B);
-  int zpm = 0;
-  for (int l = 0; l < d.L; ++l)
-    if (d.zw[l]) {
-      zpm |= 1 << l;
-      a.zw[l] = (const T*)d.zw[l];
-    }
-  a.zwld = d.zwld;
-  if (zpm && (d.C != 64 || d.slope != 0.f || d.zwld % 8)) return -1;
-  for (int l = 0; l < d.L; ++l)
-    if (d.zw[l] && (uintptr_t)d.zw[l] % 16) return -1;
-  const bool up = d.up_H > 0;
-  if (up) {
-    if (4 * d.up_H * d.up_W != d.HW || d.up_W * 2 < 16 || (d.C != 64 && d.C != 128)) return -1;
-    a.up = up2x_src(d.up_H, d.up_W);
-  }
-  dim3 grid((unsigned)((long)d.B * d.HW / a.PPW));
-  if (d.version_out) *d.version_out = 3;
-  static const int use_v4 = GHOST_KNOB("GHOST_AAD_V4", 1);
-  // v4 (prefetching) only for the through-upsample form: measured B = 64, 256x256 L = 2: 724 vs 734 us
-  // with the upsample, 604 vs 550 us without it (there v3's register loads win)
-  static const unsigned dyn_lds = GHOST_KNOB("GHOST_AAD_DYNLDS", 0u);
+  a.lda = d.lda; a.ldh = d.ldh; a.id_ld = d.id_ld; a.HW = d.HW; a.slope = d.slope; a.zwld = d.zwld;
+  a.PPW = p.ppw;
+  if (d.up_H > 0) a.up = up2x_src(d.up_H, d.up_W);
   a.tclk = d.tclk;
   a.v5_xcd = GHOST_KNOB("GHOST_V5_XCD", 1);
-  a.v5_ipw = v5_takes(d, zpm);
+  a.v5_ipw = p.ipw;
   a.v5_flags = GHOST_KNOB("GHOST_V5_FLAGS", 3);
-  static const int v5_asm = GHOST_KNOB("GHOST_V5_ASM", 1);
-  // plan log: the kernel and every parameter chosen above (a.PPW and a.v5_ipw as the launch uses them)
-#define GHOST_AAD_LOG(kernel)                                                                                  \
-  GHOST_PLAN_LOG("%s t=%s C=%d Ca=%d L=%d up=%d zpm=%d slope0=%d v5_ipw=%d ppw=%d", kernel, plan_dt(gdt<T>()),   \
-                 d.C, d.Ca, d.L, (int)up, zpm, d.slope == 0.f, a.v5_ipw, a.PPW)
-  if (a.v5_ipw && d.C == 128) {
-    a.PPW = 1024;
-    grid = dim3((unsigned)((long)d.B * d.HW / 1024 / a.v5_ipw));
-#define GHOST_V5W(l)                                                                             \
-    if (d.L == l) {                                                                              \
-      GHOST_AAD_LOG("aad_v5_wide");                                                              \
-      if (d.slope == 0.f)                                                                        \
-        hipLaunchKernelGGL((aad_v5_wide_kernel<T, 64, l, true>), grid, dim3(1024), 0, s, a);      \
-      else                                                                                       \
-        hipLaunchKernelGGL((aad_v5_wide_kernel<T, 64, l, false>), grid, dim3(1024), 0, s, a);     \
-      if (d.version_out) *d.version_out = 5;                                                     \
-      return (int)hipGetLastError();                                                             \
-    }
-    GHOST_V5W(1) GHOST_V5W(2)
-#undef GHOST_V5W
-    return -1;
-  }
-  if (a.v5_ipw) {
-    grid = dim3(grid.x / a.v5_ipw);
-#define GHOST_V5(ca, l)                                                                          \
-    if (d.Ca == ca && d.L == l && !zpm) {                                                        \
-      GHOST_AAD_LOG("aad_v5");                                                                   \
-      if (d.slope == 0.f)                                                                        \
-        hipLaunchKernelGGL((aad_v5_kernel<T, ca, l, true, 0, false>), grid, dim3(kWaves * 64), 0, s, a); \
-      else                                                                                       \
-        hipLaunchKernelGGL((aad_v5_kernel<T, ca, l, false, 0, false>), grid, dim3(kWaves * 64), 0, s, a); \
-      if (d.version_out) *d.version_out = 5;                                                     \
-      return (int)hipGetLastError();                                                             \
-    }
-    GHOST_V5(64, 1) GHOST_V5(64, 2) GHOST_V5(32, 1) GHOST_V5(32, 2)
-#undef GHOST_V5
-#define GHOST_V5Z(ca, zm)                                                                        \
-    if (d.Ca == ca && d.L == 2 && zpm == zm) {                                                   \
-      GHOST_AAD_LOG(v5_asm ? "aad_v5z_asm" : "aad_v5z");                                          \
-      if (v5_asm)                                                                                \
-        hipLaunchKernelGGL((aad_v5_kernel<T, ca, 2, true, zm, true>), grid, dim3(kWaves * 64), 0, s, a); \
-      else                                                                                       \
-        hipLaunchKernelGGL((aad_v5_kernel<T, ca, 2, true, zm, false>), grid, dim3(kWaves * 64), 0, s, a); \
-      if (d.version_out) *d.version_out = 5;                                                     \
-      return (int)hipGetLastError();                                                             \
-    }
-    GHOST_V5Z(64, 1) GHOST_V5Z(64, 2) GHOST_V5Z(64, 3) GHOST_V5Z(32, 1) GHOST_V5Z(32, 2) GHOST_V5Z(32, 3)
-#undef GHOST_V5Z
-    grid = dim3(grid.x * a.v5_ipw);   // (not reached: v5_takes admits only the shapes above)
-    a.v5_ipw = 0;
-  }
-  if constexpr (std::is_same<T, bf16>::value) {
-  if (use_v4 && up && d.C == 64 && a.PPW % 256 == 0 && d.ldh % 8 == 0) {
-#define GHOST_V4(ca, l, u)                                                                       \
-    if (d.Ca == ca && d.L == l && up == u && !zpm) {                                             \
-      GHOST_AAD_LOG("aad_v4");                                                                   \
-      if (d.slope == 0.f)                                                                        \
-        hipLaunchKernelGGL((aad_v4_kernel<ca, l, u, true>), grid, dim3(kWaves * 64), dyn_lds, s, a); \
-      else                                                                                       \
-        hipLaunchKernelGGL((aad_v4_kernel<ca, l, u, false>), grid, dim3(kWaves * 64), dyn_lds, s, a); \
-      if (d.version_out) *d.version_out = 4;                                                     \
-      return (int)hipGetLastError();                                                             \
-    }
-    GHOST_V4(64, 1, true) GHOST_V4(64, 2, true) GHOST_V4(32, 1, true) GHOST_V4(32, 2, true)
-#undef GHOST_V4
-    // AADBlk8's block-input pair with tap partials: layer 1 (last_add_block, nb >= 2) or both (nb = 1)
-#define GHOST_V4Z(ca, zm)                                                                        \
-    if (d.Ca == ca && d.L == 2 && zpm == zm) {                                                   \
-      GHOST_AAD_LOG("aad_v4z");                                                                  \
-      hipLaunchKernelGGL((aad_v4_kernel<ca, 2, true, true, zm>), grid, dim3(kWaves * 64), 0, s, a); \
-      if (d.version_out) *d.version_out = 4;                                                     \
-      return (int)hipGetLastError();                                                             \
-    }
-    GHOST_V4Z(64, 1) GHOST_V4Z(64, 2) GHOST_V4Z(64, 3) GHOST_V4Z(32, 1) GHOST_V4Z(32, 2) GHOST_V4Z(32, 3)
-#undef GHOST_V4Z
-  }
-  }
-  if (zpm) {   // the non-upsampled forms with tap partials (AADBlk8's last add_block; fuse_upsample off)
-    if (d.C == 64 && d.L == 1 && !up && zpm == 1 && (d.Ca == 64 || d.Ca == 32)) {
-      GHOST_AAD_LOG("aad_v3_zp1");
-      if (d.Ca == 64)
-        hipLaunchKernelGGL((aad_v3_zp1_kernel<T, 64>), grid, dim3(kWaves * 64), 0, s, a);
-      else
-        hipLaunchKernelGGL((aad_v3_zp1_kernel<T, 32>), grid, dim3(kWaves * 64), 0, s, a);
-      return (int)hipGetLastError();
-    }
-#define GHOST_V3Z(ca, l, zm)                                                                     \
-    if (d.C == 64 && d.Ca == ca && d.L == l && !up && zpm == zm) {                               \
-      GHOST_AAD_LOG("aad_v3z");                                                                  \
-      hipLaunchKernelGGL((aad_v3_kernel<T, 64, ca, l, false, zm>), grid, dim3(kWaves * 64), 0, s, a); \
-      return (int)hipGetLastError();                                                             \
-    }
-    GHOST_V3Z(64, 2, 1) GHOST_V3Z(32, 2, 1) GHOST_V3Z(64, 2, 2)
-    GHOST_V3Z(32, 2, 2) GHOST_V3Z(64, 2, 3) GHOST_V3Z(32, 2, 3)
-#undef GHOST_V3Z
-    return -1;
-  }
-#define GHOST_V3(c, ca, l, u)                                                                   \
-  if (d.C == c && d.Ca == ca && d.L == l && up == u) {                                          \
-    GHOST_AAD_LOG("aad_v3");                                                                    \
-    hipLaunchKernelGGL((aad_v3_kernel<T, c, ca, l, u>), grid, dim3(kWaves * 64), 0, s, a);         \
-    return (int)hipGetLastError();                                                              \
-  }
-#define GHOST_V3W(c, ca, l, u)                                                                  \
-  if (d.C == c && d.Ca == ca && d.L == l && up == u) {                                          \
-    GHOST_AAD_LOG("aad_v3_wide");                                                               \
-    hipLaunchKernelGGL((aad_v3_wide_kernel<T, c, ca, l, u>), grid, dim3(kWaves * 64), 0, s, a);    \
-    return (int)hipGetLastError();                                                              \
-  }
-  GHOST_V3(64, 64, 1, false) GHOST_V3(64, 64, 2, false) GHOST_V3(64, 32, 1, false) GHOST_V3(64, 32, 2, false)
-  // through-upsample forms: the block-input AADLayers of AADBlk8 (first add_block + last_add_block)
-  GHOST_V3(64, 64, 2, true) GHOST_V3(64, 32, 2, true) GHOST_V3(64, 64, 1, true) GHOST_V3(64, 32, 1, true)
-  GHOST_V3W(128, 128, 1, false) GHOST_V3W(128, 64, 1, false) GHOST_V3W(128, 32, 1, false)
-  // the AADBlk7 block-input pair (C = 128, Ca = 64): one pass over h_in / z_attr for both layers, h_in
-  // materialised or (UP) sampled from the 64x64 AADBlk6 output on the fly
-  GHOST_V3W(128, 64, 2, false) GHOST_V3W(128, 64, 2, true)
-  // AADBlk7's block-input AADLayers read upsample2x(AADBlk6 output) on the fly (C = 128)
-  GHOST_V3W(128, 128, 1, true) GHOST_V3W(128, 64, 1, true) GHOST_V3W(128, 32, 1, true)
-  GHOST_V3W(256, 128, 1, false) GHOST_V3W(256, 64, 1, false)
-#undef GHOST_V3W
-#undef GHOST_V3
-#undef GHOST_AAD_LOG
-  return -1;
+  GHOST_PLAN_LOG("%s", aad_v3_signature(p, d).s);
+  hipLaunchKernelGGL(fn, dim3(p.grid), dim3(p.block), p.dyn_lds, s, a);
+  return (int)hipGetLastError();
 }
 
-int aad_v3(const AadV3Desc& d, hipStream_t s) {
-  if (!aad_v3_supported(d.dt, d.B, d.HW, d.C, d.Ca, d.lda, d.ldh, d.ldo[0])) return -1;
-  if (d.L == 2 && d.ldo[1] % 8) return -1;
-  if (d.L < 1 || d.L > 2 || (d.L == 2 && d.C != 64 && !(d.C == 128 && d.Ca == 64))) return -1;
-  return d.dt == GHOST_F16 ? aad_v3_t<_Float16>(d, s) : aad_v3_t<bf16>(d, s);
+int aad_v3(const AadV3Desc& d, const AadV3Plan& p, hipStream_t s) {
+  if (p.kernel == AadV3Kernel::None) return -1;
+  for (int l = 0; l < d.L; ++l)
+    if (d.zw[l] && (uintptr_t)d.zw[l] % 16) return -1;
+  return d.dt == GHOST_F16 ? aad_v3_t<_Float16>(d, p, s) : aad_v3_t<bf16>(d, p, s);
 }
+
+int aad_v3(const AadV3Desc& d, hipStream_t s) { return aad_v3(d, aad_v3_plan(d), s); }
 
 // ---------------------------------------------------------------------------------------------
 // AADBlk8's output conv from the tap partials (tap_rows.h): output (y, x) is the sum over both producers'

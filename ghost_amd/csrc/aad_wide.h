@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "plan_log.h"
+
 namespace ghost {
 
 struct AadWideDesc {
@@ -21,6 +23,19 @@ struct AadWideDesc {
   int dt = 1;                                  // storage type: GHOST_BF16 (1) or GHOST_F16 (2)
 };
 
+// What a launch of a descriptor runs, decided from its integers (dt, B, HW, C, Ca, the leading dimensions) and
+// from whether za and w3 are 16-byte aligned (aad_gemm's DMA needs it; without it the launch takes aad_wide)
+enum class AadWideKernel { None, Gemm, Wide, WideDeep };
+struct AadWidePlan {
+  AadWideKernel kernel = AadWideKernel::None;   // None: no kernel takes this descriptor
+  int ppw = 0;                                  // pixels per workgroup (aad_wide, aad_wide_deep)
+  unsigned grid = 0, block = 0;
+};
+AadWidePlan aad_wide_plan(const AadWideDesc& d, bool ptrs_aligned16);
+PlanSig aad_wide_signature(const AadWidePlan& p, const AadWideDesc& d);   // the plan-log line of (plan, desc)
+
+bool aad_wide_shape(int C, int Ca);   // the (C, Ca) with a kernel here
+// true when a launch of this shape has a plan (whatever its pointers' alignment)
 bool aad_wide_supported(int dt, int B, int HW, int C, int Ca, int lda, int ldh, int ldo);
 int aad_wide(const AadWideDesc& d, hipStream_t s);
 

@@ -8,6 +8,8 @@
 // (ops.hip), so a 16-pixel tile here is one round trip: z_attr row, the tile's 64 channels of
 // h_in and the mask.  The C/64 workgroups of one pixel block are adjacent in launch order (and
 // on one XCD), so their shared z_attr reads are L2 hits.
+#include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 
 #include "aad_wide.h"
@@ -318,11 +320,10 @@ __global__ void __launch_bounds__(256) aad_gemm_kernel(const AadWideArgs a, int 
   }
 }
 
-namespace {
-int wide_ppw(int B, int HW, int C, int Ca) {
-  // as many pixels per workgroup as keep a full round of workgroups (two per CU; one for the
-  // 133 KB Ca = 512 rows): the weight rows staged per workgroup are then amortised over as
-  // many 16-pixel tiles as possible
+// host side: aad_wide_plan decides (kernel, pixels per workgroup, grid, block); aad_wide launches the plan
+static int wide_ppw(int B, int HW, int C, int Ca) {
+  // as many pixels per workgroup as keep a full round of workgroups (two per CU; one for the 133 KB Ca = 512 rows):
+  // the weight rows staged per workgroup are then amortised over as many 16-pixel tiles as possible
   const long minwg = Ca > 256 ? 256 : 512;
   static const int force = GHOST_KNOB("GHOST_AAD_WIDE_PPW", 0);
   if (force > 0 && HW % force == 0 && force % 16 == 0) return force;
@@ -331,69 +332,70 @@ int wide_ppw(int B, int HW, int C, int Ca) {
     if (HW % ppw == 0 && (best == 0 || (long)B * HW / ppw * (C / 64) >= minwg)) best = ppw;
   return best;
 }
-}  // namespace
 
-bool aad_wide_supported(int dt, int B, int HW, int C, int Ca, int lda, int ldh, int ldo) {
-  if (!is16(dt)) return false;
-  const bool shape = (C == 256 || C == 512 || C == 1024) && (Ca == 64 || Ca == 128 || Ca == 256 || Ca == 512);
-  if (!shape || lda % 8 || ldh % 8 || ldo % 8) return false;
-  const int ppw = wide_ppw(B, HW, C, Ca);
-  return ppw > 0 && (long)B * HW / ppw * (C / 64) >= 256;
+bool aad_wide_shape(int C, int Ca) {
+  return (C == 256 || C == 512 || C == 1024) && (Ca == 64 || Ca == 128 || Ca == 256 || Ca == 512);
 }
 
-static bool aad_gemm_ok(const AadWideDesc& d) {
-  static const int on = GHOST_KNOB("GHOST_AAD_GEMM", 1);
-  // Ca = 512 only: at Ca = 256 (the 32x32 stage) four K stages do not amortise the tile's prologue and
-  // epilogue at one workgroup per CU (measured 80-86 us against aad_wide's 52-57 us; Ca = 512: 62-66
-  // against 78-83 us)
+AadWidePlan aad_wide_plan(const AadWideDesc& d, bool ptrs_aligned16) {
+  typedef AadWideKernel K;
+  if (!is16(d.dt) || !aad_wide_shape(d.C, d.Ca) || d.lda % 8 || d.ldh % 8 || d.ldo % 8) return {};
+  const int ppw = wide_ppw(d.B, d.HW, d.C, d.Ca);
+  if (ppw <= 0 || (long)d.B * d.HW / ppw * (d.C / 64) < 256) return {};
+  static const int gemm = GHOST_KNOB("GHOST_AAD_GEMM", 1);
+  // aad_gemm at Ca = 512 only: at Ca = 256 (the 32x32 stage) four K stages do not amortise the tile's prologue and
+  // epilogue at one workgroup per CU (measured 80-86 us against aad_wide's 52-57 us; Ca = 512: 62-66 against 78-83 us)
   // and only where the 256 x 256 tiles make half a round of workgroups: at B = 1 the 16 x 16 stage is 8 of them
   // (28-32 us each, profiles/r05_step_trace_b1.txt); aad_wide's 16-pixel workgroups spread the layer over the CUs
   const long wgs = (long)d.B * d.HW / 256 * (d.C / 128);
-  return on && d.HW % 256 == 0 && d.C % 128 == 0 && d.Ca == 512 && d.lda % 8 == 0 &&
-         d.ldh % 8 == 0 && d.ldo % 8 == 0 && (uintptr_t)d.za % 16 == 0 && (uintptr_t)d.w3 % 16 == 0 && wgs >= 128;
+  if (gemm && ptrs_aligned16 && d.HW % 256 == 0 && d.Ca == 512 && wgs >= 128) return {K::Gemm, 0, (unsigned)wgs, 256};
+  return {d.Ca == 512 ? K::WideDeep : K::Wide, ppw, (unsigned)((long)d.B * d.HW / ppw * (d.C / 64)), kWideWaves * 64};
 }
 
+bool aad_wide_supported(int dt, int B, int HW, int C, int Ca, int lda, int ldh, int ldo) {
+  AadWideDesc d;
+  d.dt = dt; d.B = B; d.HW = HW; d.C = C; d.Ca = Ca; d.lda = lda; d.ldh = ldh; d.ldo = ldo;
+  return aad_wide_plan(d, false).kernel != AadWideKernel::None;
+}
+
+PlanSig aad_wide_signature(const AadWidePlan& p, const AadWideDesc& d) {
+  PlanSig g;
+  if (p.kernel == AadWideKernel::Gemm) snprintf(g.s, sizeof(g.s), "aad_gemm t=%s C=%d Ca=%d", plan_dt(d.dt), d.C, d.Ca);
+  else snprintf(g.s, sizeof(g.s), "%s t=%s C=%d Ca=%d ppw=%d", p.kernel == AadWideKernel::Wide ? "aad_wide" : "aad_wide_deep",
+                plan_dt(d.dt), d.C, d.Ca, p.ppw);
+  return g;
+}
+
+// every instantiation, once (C = 0: the kernel takes C as its second argument)
 template <typename T>
-static int aad_wide_t(const AadWideDesc& d, hipStream_t s);
+static const void* aad_wide_fn(const AadWidePlan& p, const AadWideDesc& d) {
+  static const struct Row { AadWideKernel kernel; int C, Ca; const void* fn; } rows[] = {
+#define GHOST_W(c, ca) {AadWideKernel::Wide, c, ca, (const void*)aad_wide_kernel<T, c, ca>},
+#define GHOST_WD(c, ca) {AadWideKernel::WideDeep, c, ca, (const void*)aad_wide_deep_kernel<T, c, ca>},
+      GHOST_W(256, 64) GHOST_W(256, 128) GHOST_W(256, 256) GHOST_W(512, 64) GHOST_W(512, 128) GHOST_W(512, 256)
+      GHOST_W(1024, 64) GHOST_W(1024, 128) GHOST_W(1024, 256) GHOST_WD(512, 512) GHOST_WD(1024, 512)
+#undef GHOST_WD
+#undef GHOST_W
+      {AadWideKernel::Gemm, 0, 512, (const void*)aad_gemm_kernel<T, 512>}};
+  for (const Row& r : rows)
+    if (r.kernel == p.kernel && (r.C == 0 || r.C == d.C) && r.Ca == d.Ca) return r.fn;
+  return nullptr;
+}
 
 int aad_wide(const AadWideDesc& d, hipStream_t s) {
-  if (!aad_wide_supported(d.dt, d.B, d.HW, d.C, d.Ca, d.lda, d.ldh, d.ldo) || !d.mask) return -1;
-  return d.dt == GHOST_F16 ? aad_wide_t<_Float16>(d, s) : aad_wide_t<bf16>(d, s);
-}
-
-template <typename T>
-static int aad_wide_t(const AadWideDesc& d, hipStream_t s) {
+  const AadWidePlan p = aad_wide_plan(d, (uintptr_t)d.za % 16 == 0 && (uintptr_t)d.w3 % 16 == 0);
+  const void* fn = d.dt == GHOST_F16 ? aad_wide_fn<_Float16>(p, d) : aad_wide_fn<bf16>(p, d);
+  if (!fn || !d.mask) return -1;
   AadWideArgs a{};
   a.za = d.za; a.hin = d.hin; a.stat = d.stat;
   a.w3 = d.w3; a.b3 = d.b3; a.wh = d.wh; a.bh = d.bh; a.idgb = d.idgb; a.mask = d.mask; a.out = d.out;
   a.lda = d.lda; a.ldh = d.ldh; a.ldo = d.ldo; a.id_ld = d.id_ld; a.HW = d.HW; a.slope = d.slope;
-  if (aad_gemm_ok(d)) {
-    dim3 g((unsigned)((long)d.B * d.HW / 256 * (d.C / 128)));
-    GHOST_PLAN_LOG("aad_gemm t=%s C=%d Ca=%d", plan_dt(gdt<T>()), d.C, d.Ca);
-    hipLaunchKernelGGL((aad_gemm_kernel<T, 512>), g, dim3(256), 0, s, a, d.C);
-    return (int)hipGetLastError();
-  }
-  a.PPW = wide_ppw(d.B, d.HW, d.C, d.Ca);
-  a.nblk = (int)((long)d.B * d.HW / a.PPW);
-  dim3 grid((unsigned)(a.nblk * (d.C / 64)));
-#define GHOST_W(c, ca)                                                                 \
-  if (d.C == c && d.Ca == ca) {                                                        \
-    GHOST_PLAN_LOG("aad_wide t=%s C=%d Ca=%d ppw=%d", plan_dt(gdt<T>()), c, ca, a.PPW); \
-    hipLaunchKernelGGL((aad_wide_kernel<T, c, ca>), grid, dim3(kWideWaves * 64), 0, s, a); \
-    return (int)hipGetLastError();                                                     \
-  }
-  GHOST_W(256, 64) GHOST_W(256, 128) GHOST_W(256, 256) GHOST_W(512, 64) GHOST_W(512, 128) GHOST_W(512, 256)
-  GHOST_W(1024, 64) GHOST_W(1024, 128) GHOST_W(1024, 256)
-#undef GHOST_W
-#define GHOST_WD(c, ca)                                                                     \
-  if (d.C == c && d.Ca == ca) {                                                             \
-    GHOST_PLAN_LOG("aad_wide_deep t=%s C=%d Ca=%d ppw=%d", plan_dt(gdt<T>()), c, ca, a.PPW); \
-    hipLaunchKernelGGL((aad_wide_deep_kernel<T, c, ca>), grid, dim3(kWideWaves * 64), 0, s, a); \
-    return (int)hipGetLastError();                                                          \
-  }
-  GHOST_WD(512, 512) GHOST_WD(1024, 512)
-#undef GHOST_WD
-  return -1;
+  a.PPW = p.ppw; a.nblk = p.ppw ? (int)((long)d.B * d.HW / p.ppw) : 0;
+  GHOST_PLAN_LOG("%s", aad_wide_signature(p, d).s);
+  int C = d.C;
+  void* args[] = {&a, &C};   // (a) or, aad_gemm, (a, C)
+  (void)hipLaunchKernel(fn, dim3(p.grid), dim3(p.block), args, 0, s);
+  return (int)hipGetLastError();
 }
 
 }  // namespace ghost

@@ -17,6 +17,7 @@
 
 #include "../../include/ghost_amd.h"
 #include "aad_fused.h"
+#include "aad_path.h"
 #include "aad_v3.h"
 #include "conv_halo.h"
 #include "aad_wide.h"
@@ -92,7 +93,7 @@ struct ghost_aei {
   int ev_used = 0;
   ProfClass prof[8];
   // in-kernel clock of the roofline kernel's launches (profiling class 1): per launch a region of per-workgroup
-  // start and per-wave end stamps (aad_v3_clock_words); clk_cap words of device buffer, bump-allocated
+  // start and per-wave end stamps (AadV3Plan::clock_words); clk_cap words of device buffer, bump-allocated
   unsigned long long* clk = nullptr;
   size_t clk_cap = 0, clk_used = 0;
   int clk_dev = -1;
@@ -104,11 +105,6 @@ struct ghost_aei {
     unsigned long long* p = clk + clk_used;
     clk_used += (size_t)words;
     return p;
-  }
-  void drop_last_clk() {
-    if (clk_launch.empty()) return;
-    clk_used = clk_launch.back().first;
-    clk_launch.pop_back();
   }
 
   typedef int Pair[2];
@@ -455,9 +451,9 @@ struct GenShared {
   float* idgb;
 };
 
-// one AADLayer (+ fused ReLU) -> out
+// one AADLayer (+ fused ReLU) -> out, by the fused kernel or the mask pass + the GEMM with the blend epilogue
 void aad(Ctx& c, const std::string& name, const void* hin, int ldh, const float* stat, const void* za, int lda,
-         int Ca, int B, int n, int C, int id_off, const float* idgb, void* out, int ldo,
+         int Ca, int B, int n, int C, int id_off, const float* idgb, void* out, int ldo, bool fused,
          const float* pre_mask = nullptr) {
   ghost_aei* h = c.h;
   const double P = (double)B * n * n;
@@ -467,7 +463,7 @@ void aad(Ctx& c, const std::string& name, const void* hin, int ldh, const float*
   const float* gbb = (const float*)c.W(name + ".gbb");
   const float* wh = (const float*)c.W(name + ".wh");
   const float* bh = (const float*)c.W(name + ".bh");
-  if (aad_fused_supported(h->dt, B, n * n, C, Ca, lda, ldh, ldo)) {
+  if (fused) {
     if (!c.ok() || c.dry) return;
     int e_all = c.prof_begin(0);
     int e_big = -1;
@@ -516,15 +512,18 @@ void aad_group(Ctx& c, const std::vector<AadOut>& ls, const void* hin, int ldh, 
                int lda, int Ca, int B, int n, int C, const float* idgb, bool up_src = false,
                float* const* pre_masks = nullptr) {
   ghost_aei* h = c.h;
-  bool v3 = aad_v3_supported(h->dt, B, n * n, C, Ca, lda, ldh, 8);
-  for (auto& l : ls) v3 = v3 && l.ldo % 8 == 0;
-  if (up_src && !v3) {
+  if (ls.empty() || ls.size() > 2) {
+    c.check(GHOST_EINVAL, "aad_group: one or two layers");
+    return;
+  }
+  const int ldo[2] = {ls[0].ldo, ls.back().ldo};
+  const AadPath path = aad_path(h->dt, B, n * n, C, Ca, lda, ldh, ldo, (int)ls.size());
+  if (up_src && path != AadPath::V3) {
     c.check(GHOST_EINVAL, "aad_group: through-upsample input needs the v3 kernel");
     return;
   }
-  if (!v3) {
-    bool wide = aad_wide_supported(h->dt, B, n * n, C, Ca, lda, ldh, 8) && ls.size() <= 2;
-    for (auto& l : ls) wide = wide && l.ldo % 8 == 0;
+  if (path != AadPath::V3) {
+    const bool wide = path == AadPath::Wide;
     // the masks of every layer of the group from one pass over h_in
     float* masks[2] = {nullptr, nullptr};
     if (wide && pre_masks) {
@@ -546,7 +545,7 @@ void aad_group(Ctx& c, const std::vector<AadOut>& ls, const void* hin, int ldh, 
     for (size_t li = 0; li < ls.size(); ++li) {
       const AadOut& l = ls[li];
       if (!wide) {
-        aad(c, l.name, hin, ldh, stat, za, lda, Ca, B, n, C, l.id_off, idgb, l.out, l.ldo,
+        aad(c, l.name, hin, ldh, stat, za, lda, Ca, B, n, C, l.id_off, idgb, l.out, l.ldo, path == AadPath::Fused,
             pre_masks ? pre_masks[li] : nullptr);
         continue;
       }
@@ -572,7 +571,7 @@ void aad_group(Ctx& c, const std::vector<AadOut>& ls, const void* hin, int ldh, 
   // AADBlk7's block-input pair (C = 128, Ca = 64; h_in materialised or sampled through the upsample) in one
   // kernel: measured B = 64, 258 vs 2 x 141 us materialised (GHOST_AAD_PAIR128=0: one layer per kernel)
   static const int pair128 = GHOST_KNOB("GHOST_AAD_PAIR128", 1);
-  const size_t lmax = (C == 64 || (pair128 && C == 128 && Ca == 64)) ? 2 : 1;
+  const size_t lmax = (C == 128 && !pair128) ? 1 : (size_t)aad_v3_max_layers(C, Ca);
   for (size_t i0 = 0; i0 < ls.size(); i0 += lmax) {
     AadV3Desc d;
     d.dt = h->dt;
@@ -603,12 +602,14 @@ void aad_group(Ctx& c, const std::vector<AadOut>& ls, const void* hin, int ldh, 
     int e_all = c.prof_begin(0);
     // class 1: the block-input AAD kernel at 256x256 (reads h_in through the x2 upsample; one or two layers)
     int e_big = (n == 256 && up_src) ? c.prof_begin(1) : -1;
-    if (e_big >= 0 && h->clk_dev == c.dev) d.tclk = h->next_clk(aad_v3_clock_words(d));
-    if (e_big >= 0) d.version_out = &h->roof_version;
-    c.check(aad_v3(d, c.s), "aad_v3");
-    // only the v4 / v5 kernels write clock stamps: a launch that fell back to v3 gives its region back, so
-    // ghost_aei_profile_clock never reads unwritten words
-    if (d.tclk && h->roof_version != 4 && h->roof_version != 5) h->drop_last_clk();
+    // only the v4 / v5 kernels write clock stamps: a generation-3 plan has no clock words and reserves no region,
+    // so ghost_aei_profile_clock never reads unwritten words
+    const AadV3Plan p = aad_v3_plan(d);
+    if (e_big >= 0) {
+      h->roof_version = p.version;
+      if (h->clk_dev == c.dev) d.tclk = h->next_clk(p.clock_words);
+    }
+    c.check(aad_v3(d, p, c.s), "aad_v3");
     if (e_big >= 0) c.prof_end(1, e_big, bytes, flops);
     if (e_all >= 0) c.prof_end(0, e_all, bytes, flops);
   }
@@ -871,10 +872,8 @@ void declare_slots(ghost_aei* h) {
     const std::string blk = "gen.blk" + std::to_string(k);
     int Ca_k, n_k;
     h->attr_geom(k, Ca_k, n_k);
-    // permuted register-epilogue AAD layouts (pack.py pack_aad_v3): aad_v3 for C in {64, 128},
-    // aad_wide for C in {256, 512, 1024} with Ca <= 512
-    const bool v3 = is16(h->dt) && (cin == 64 || cin == 128 ||
-                                            ((cin == 256 || cin == 512 || cin == 1024) && Ca_k <= 512));
+    // permuted register-epilogue AAD layouts (pack.py pack_aad_v3) where aad_v3 or aad_wide has a kernel
+    const bool v3 = aad_reg_layout(h->dt, cin, Ca_k);
     for (int i = 0; i < h->nb; ++i) {
       const std::string an = blk + ".aad" + std::to_string(i);
       add(an + ".gbw"); add(an + ".gbb"); add(an + ".wh"); add(an + ".bh");
@@ -1500,7 +1499,8 @@ extern "C" int ghost_aad_layer_nhwc(int dtype, const void* h_in, int ldh, const 
   char* scratch = base + stat_b + mask_b;
   int rc = in_stats(dtype, h_in, ldh, B, HW, C, stat, scratch, sc, s);
   if (rc) return fail(rc, "aad_layer: in_stats failed");
-  if (aad_fused_supported(dtype, B, HW, C, Ca, lda, ldh, ldo)) {
+  // this entry takes gbw, not the w3 / b3 layout: Fused or Split
+  if (aad_path(dtype, B, HW, C, Ca, lda, ldh, &ldo, 1, false) == AadPath::Fused) {
     rc = aad_fused(dtype, z_attr, lda, Ca, gbw_packed, Kpad, gbb, h_in, ldh, stat, wh, bh, idgb, id_ld, out, ldo, B, HW, C,
                    slope, s);
     return rc ? fail(rc, "aad_layer: fused kernel failed") : 0;
@@ -1550,12 +1550,11 @@ extern "C" int ghost_aad_layers_v3_dt_nhwc(int dtype, const void* h_in, int ldh,
   if (up2x && (H % 2 || W % 2 || (C != 64 && C != 128)))
     return fail(GHOST_EINVAL, "aad_v3: up2x needs even H, W and C in {64, 128}");
   // aad_wide: one layer, C in {256, 512, 1024}, Ca <= 512, where the all-channel kernel does not fit
-  const bool wide = C >= 256 && !aad_v3_supported(dtype, B, HW, C, Ca, lda, ldh, ldo[0]);
-  if (wide && (L != 1 || up2x || !aad_wide_supported(dtype, B, HW, C, Ca, lda, ldh, ldo[0])))
-    return fail(GHOST_EINVAL, "aad_wide: unsupported shape (one layer, C in {256,512,1024}, Ca <= 512)");
-  for (int l = 0; l < L && !wide; ++l)
-    if (!aad_v3_supported(dtype, B, HW, C, Ca, lda, ldh, ldo[l]))
-      return fail(GHOST_EINVAL, "aad_v3: unsupported shape (bf16 / fp16, C in {64,128}, enough pixels)");
+  const AadPath path = aad_path(dtype, B, HW, C, Ca, lda, ldh, ldo, L);
+  const bool wide = path == AadPath::Wide;
+  if (wide ? (L != 1 || up2x) : path != AadPath::V3)
+    return fail(GHOST_EINVAL, "aad_v3 / aad_wide: unsupported shape (bf16 / fp16, a planner's (C, Ca), enough pixels; "
+                              "aad_wide: one layer, no upsample)");
   const size_t stat_b = ((size_t)B * C * 2 * sizeof(float) + 255) & ~size_t(255);
   const size_t sc = in_stats_workspace_bytes(B, HW, C);
   char* base = (char*)(((uintptr_t)ws + 255) & ~uintptr_t(255));
@@ -1602,6 +1601,36 @@ extern "C" int ghost_aad_layers_v3_nhwc(const void* h_in, int ldh, int up2x, con
                                         int64_t ws_bytes, void* stream) {
   return ghost_aad_layers_v3_dt_nhwc(GHOST_BF16, h_in, ldh, up2x, z_attr, lda, B, H, W, C, Ca, L, w3, b3, wh, bh, idgb,
                                      id_ld, slope, out, ldo, ws, ws_bytes, stream);
+}
+
+extern "C" int64_t ghost_aad_plan(int dtype, int B, int H, int W, int C, int Ca, int L, int up2x, int zp_mask,
+                                  float slope, int lda, int ldh, const int ldo[], char* buf, int64_t cap) {
+  if (L < 1 || L > 2 || !ldo || (up2x & ~1) || (zp_mask & ~3) || cap < 0 || (cap > 0 && !buf))
+    return fail(GHOST_EINVAL, "aad_plan: bad argument");
+  const int HW = H * W;
+  PlanSig sig;
+  sig.s[0] = 0;
+  const AadPath path = aad_path(dtype, B, HW, C, Ca, lda, ldh, ldo, L);
+  if (path == AadPath::V3) {
+    AadV3Desc d;
+    d.dt = dtype; d.B = B; d.HW = HW; d.C = C; d.Ca = Ca; d.L = L; d.lda = lda; d.ldh = ldh; d.slope = slope;
+    if (up2x) { d.up_H = H / 2; d.up_W = W / 2; }
+    for (int l = 0; l < L; ++l) {
+      d.ldo[l] = ldo[l];
+      if (zp_mask >> l & 1) d.zw[l] = &sig;   // the planner asks only whether it is set
+    }
+    d.zwld = 2 * C;   // the narrow conv layout's row of both K halves
+    const AadV3Plan p = aad_v3_plan(d);
+    if (p.kernel != AadV3Kernel::None) sig = aad_v3_signature(p, d);
+  } else if (path == AadPath::Wide && !up2x && !zp_mask) {
+    AadWideDesc d;
+    d.dt = dtype; d.B = B; d.HW = HW; d.C = C; d.Ca = Ca; d.lda = lda; d.ldh = ldh; d.ldo = ldo[0]; d.slope = slope;
+    const AadWidePlan p = aad_wide_plan(d, true);
+    if (p.kernel != AadWideKernel::None) sig = aad_wide_signature(p, d);
+  }
+  if (!sig.s[0]) return fail(GHOST_EINVAL, "aad_plan: no aad_v3 / aad_wide kernel takes this shape");
+  if (cap > 0) snprintf(buf, (size_t)cap, "%s", sig.s);
+  return (int64_t)strlen(sig.s) + 1;
 }
 
 extern "C" int ghost_aad_mask_nhwc(int dtype, const void* h, int ldh, int B, int HW, int C, float* stat, const float* wh0,

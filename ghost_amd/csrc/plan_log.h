@@ -12,6 +12,9 @@ namespace ghost {
 extern std::atomic<int> g_plan_log_on;
 void plan_log_append(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 
+// one signature, formatted by a launcher's own function (only while the log is on, or for ghost_aad_plan)
+struct PlanSig { char s[160]; };
+
 // "bf16" / "f16" / "f32" of a GhostDType
 inline const char* plan_dt(int dt) { return dt == 1 ? "bf16" : dt == 2 ? "f16" : dt == 0 ? "f32" : "u8"; }
 

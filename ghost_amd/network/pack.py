@@ -142,7 +142,9 @@ def pack_aad_v3(sd, prefix: str, dtype) -> Dict[str, torch.Tensor]:
 
 def v3_layout(c: int, ca: int) -> bool:
     """AADLayers packed for the register-epilogue kernels too: aad_v3 (C in {64, 128}) and
-    aad_wide (C in {256, 512, 1024}, Ca <= 512); mirrors aei_runtime.hip declare_slots."""
+    aad_wide (C in {256, 512, 1024}, Ca <= 512).  The runtime declares the w3 / b3 slots by aad_reg_layout
+    (csrc/aad_path.h: the (C, Ca) one of the two planners has a kernel for), which Python cannot include; the two
+    agree on every AADLayer of unet, linknet and resnet (tests/test_host_cpu.py test_pack_slots_match_runtime_plan)."""
     return c in (64, 128) or (c in (256, 512, 1024) and ca <= 512)
 
 

@@ -422,6 +422,14 @@ int ghost_face_masks(const int32_t* poly, const int32_t* nv, const int32_t* para
  * bytes needed including the NUL; buf = NULL asks for the size. */
 int ghost_plan_log(int enable);
 int64_t ghost_plan_log_read(char* buf, int64_t cap);
+/* Test support, touches no device: the signature that a ghost_aad_layers_v3_dt_nhwc launch (or the runtime's launch)
+ * of this shape would append to the plan log, from the same path rule, planners and formatter as the launch.
+ * L = 1 or 2 AADLayers with ldo[L]; up2x = 1: h_in read through the x2 upsample of an [H/2, W/2] source;
+ * zp_mask bit l: layer l writes tap partials.  Copies the NUL-terminated text into buf (at most cap bytes;
+ * buf = NULL with cap = 0 asks for the size) and returns the bytes needed including the NUL, or GHOST_EINVAL when
+ * neither aad_v3 nor aad_wide takes the shape (the fused kernel or the mask pass + GEMM epilogue would). */
+int64_t ghost_aad_plan(int dtype, int B, int H, int W, int C, int Ca, int L, int up2x, int zp_mask, float slope,
+                       int lda, int ldh, const int ldo[], char* buf, int64_t cap);
 
 #ifdef __cplusplus
 }

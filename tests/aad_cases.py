@@ -15,8 +15,9 @@ from oracle import aei_ref
 SENTINEL = 7.0
 ULP = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -10}      # one ulp of the storage type at |x| in [1, 2)
 TNAME = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+BF, HF = torch.bfloat16, torch.float16
 C_ID = 512
-PAD = 8          # pad channels of h_in, z_attr and (first layer) out; the second layer's out pads 2 * PAD
+PAD = 8         # pad channels of h_in, z_attr and (first layer) out; the second layer's out pads 2 * PAD
 
 
 def closed_form_stats(dt, Hs, Ws, C, ldx):
@@ -354,3 +355,85 @@ def run_mask(lib, dt, h, stat, whs, bhs, small):
                                  int(small), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     return rc, [m.cpu() for m in masks], std.cpu()
+
+
+# ----------------------------------------------------------------------------------------
+# blend cases (tests/test_aad_ops.py on the GPU, tests/test_aad_plan_cpu.py without one): the smallest shapes that
+# select each variant, derived from the planners aad_v3_plan (aad_v3.hip) and aad_wide_plan (aad_wide.hip) behind
+# aad_path (aad_path.h).  If a retuned heuristic moves a case to another kernel, test_aad_plan_cpu.py says so
+# without a GPU: change the shape, not the kernel.
+#   * a bf16 C = 64 through-upsample launch always runs aad_v5 or aad_v4 (v4 takes every such launch v5 leaves),
+#     so no bf16 shape, with W / 2 % 4 != 0 or otherwise, reaches aad_v3's C = 64 UP form; fp16 has no v4, and the
+#     fp16 launches at the v4 shape below are that form's cases (they must log aad_v3).
+#   * cpu = True: the float64 reference is oracle/aei_ref.aad_layer on the CPU (at least the smallest case of
+#     every kernel); otherwise the same expression on the device.  aad_v5_wide (33 M output elements at its
+#     smallest) and aad_gemm (4 M elements behind 1024 x 512 weights) are device-only: their CPU evaluation
+#     takes many seconds.
+# ----------------------------------------------------------------------------------------
+CASES = []
+
+
+def _add(kernel, dt, c, ca, H, W, B, L, up, slope, ipw=0, ppw=None, cpu=False):
+    CASES.append(dict(kernel=kernel, dt=dt, c=c, ca=ca, H=H, W=W, B=B, L=L, up=up, slope=slope, ipw=ipw, ppw=ppw,
+                      cpu=cpu))
+
+
+for _ca in (64, 32):
+    for _L in (1, 2):
+        for _s in (0.0, 1.0):
+            _add("aad_v3", BF, 64, _ca, 64, 128, 2, _L, 0, _s, ppw=512, cpu=True)
+            # v4: HW < 65536 keeps v5 away
+            _add("aad_v4", BF, 64, _ca, 64, 128, 2, _L, 1, _s, ppw=512, cpu=True)
+            # v5: HW = 65536 (1024-pixel work items); a wide image (one row tile per item) and a narrow one (four)
+            _add("aad_v5", BF, 64, _ca, 128, 512, 2, _L, 1, _s, ipw=1, ppw=1024, cpu=(_ca, _L, _s) == (32, 1, 0.0))
+            _add("aad_v5", BF, 64, _ca, 512, 128, 2, _L, 1, _s, ipw=1, ppw=1024)
+        # two work items per workgroup need B * HW / 2048 >= 256
+        _add("aad_v5", BF, 64, _ca, 256, 256, 8, _L, 1, 0.0, ipw=2, ppw=1024)
+_add("aad_v5", BF, 64, 64, 256, 256, 8, 2, 1, 1.0, ipw=2, ppw=1024)
+_add("aad_v5", BF, 64, 32, 256, 256, 8, 1, 1, 1.0, ipw=2, ppw=1024)
+# C = 128: B * HW = 8192 is the least aad_v3_supported admits (32 workgroups of 256 pixels); neither v5_wide
+# (needs 256 work items) nor v4 (C = 64) takes the through-upsample forms here
+for _s in (0.0, 1.0):
+    for _up in (0, 1):
+        for _ca in (128, 64, 32):
+            _add("aad_v3_wide", BF, 128, _ca, 32, 128, 2, 1, _up, _s, ppw=256, cpu=True)
+        _add("aad_v3_wide", BF, 128, 64, 32, 128, 2, 2, _up, _s, ppw=256, cpu=True)
+    for _ca in (128, 64):
+        _add("aad_v3_wide", BF, 256, _ca, 32, 32, 8, 1, 0, _s, ppw=256, cpu=True)
+# v5_wide: a 64 x 64 output is 4 work items; 256 / 512 / 1024 of them select 1 / 2 / 4 per workgroup
+for _L in (1, 2):
+    for _s in (0.0, 1.0):
+        _add("aad_v5_wide", BF, 128, 64, 64, 64, 64, _L, 1, _s, ipw=1, ppw=1024)
+_add("aad_v5_wide", BF, 128, 64, 64, 64, 128, 2, 1, 0.0, ipw=2, ppw=1024)
+_add("aad_v5_wide", BF, 128, 64, 64, 64, 256, 1, 1, 0.0, ipw=4, ppw=1024)
+for _s in (0.0, 1.0):
+    _add("aad_wide", BF, 256, 128, 16, 16, 16, 1, 0, _s, ppw=32, cpu=True)
+    _add("aad_wide", BF, 512, 64, 32, 32, 4, 1, 0, _s, ppw=64, cpu=True)
+    _add("aad_wide_deep", BF, 1024, 512, 16, 16, 8, 1, 0, _s, ppw=128, cpu=_s == 0.0)
+    _add("aad_gemm", BF, 1024, 512, 16, 16, 16, 1, 0, _s)
+# fp16: one case per kernel family; v4 is bf16-only, so its shape must log aad_v3 (the C = 64 UP form)
+_add("aad_v3", HF, 64, 64, 64, 128, 2, 2, 0, 0.0, ppw=512, cpu=True)
+_add("aad_v3", HF, 64, 64, 64, 128, 2, 2, 1, 0.0, ppw=512, cpu=True)
+_add("aad_v3", HF, 64, 32, 64, 128, 2, 1, 1, 1.0, ppw=512, cpu=True)
+_add("aad_v5", HF, 64, 64, 128, 512, 2, 2, 1, 0.0, ipw=1, ppw=1024)
+_add("aad_v3_wide", HF, 128, 64, 32, 128, 2, 2, 1, 0.0, ppw=256, cpu=True)
+_add("aad_v3_wide", HF, 256, 128, 32, 32, 8, 1, 0, 0.0, ppw=256, cpu=True)
+_add("aad_v5_wide", HF, 128, 64, 64, 64, 64, 1, 1, 0.0, ipw=1, ppw=1024)
+_add("aad_wide", HF, 256, 128, 16, 16, 16, 1, 0, 0.0, ppw=32, cpu=True)
+_add("aad_wide_deep", HF, 1024, 512, 16, 16, 8, 1, 0, 0.0, ppw=128)
+_add("aad_gemm", HF, 1024, 512, 16, 16, 16, 1, 0, 0.0)
+
+
+def _id(k):
+    return (f"{k['kernel']}-{TNAME[k['dt']]}-C{k['c']}-Ca{k['ca']}-{k['H']}x{k['W']}-B{k['B']}-L{k['L']}-up{k['up']}"
+            f"-slope{k['slope']:g}")
+
+
+def _tokens(k):
+    t = [f"t={TNAME[k['dt']]}", f"C={k['c']}", f"Ca={k['ca']}"]
+    if k["kernel"] in ("aad_wide", "aad_wide_deep"):
+        return t + [f"ppw={k['ppw']}"]
+    if k["kernel"] == "aad_gemm":
+        return t
+    return t + [f"L={k['L']}", f"up={k['up']}", "zpm=0", f"slope0={int(k['slope'] == 0.0)}", f"v5_ipw={k['ipw']}",
+                f"ppw={k['ppw']}"]
