@@ -101,6 +101,8 @@ _SIGS = {
     "ghost_aad_mask_nhwc": (i32, [i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "ghost_conv3x3_narrow_nhwc": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, i32, vp,
                                         vp]),
+    "ghost_norm_modulate_nhwc": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, f32, i32, vp, i32, vp]),
+    "ghost_lip_pool_nhwc": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     "ghost_plan_log": (i32, [i32]),
     "ghost_plan_log_read": (i64, [C.c_char_p, i64]),
     "ghost_aad_plan": (i64, [i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, C.POINTER(i32), C.c_char_p, i64]),

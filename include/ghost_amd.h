@@ -26,6 +26,9 @@
  *   network/AEI_Net.py:94,125    F.interpolate(x2, bilinear, align_corners) -> ghost_upsample2x_nhwc
  *   utils/inference/video_processing.py:134,163,184 + utils/inference/image_processing.py:18-19
  *                                cv2.warpAffine(frame, M, (224, 224)) + cv2.resize(crop, (256, 256)) -> ghost_align_crops_u8
+ *   models/networks/normalization.py:93-107  SPADE: BN(x) * gamma + beta (+ InstanceNorm / activation / nearest x2)
+ *                                                                          -> ghost_norm_modulate_nhwc
+ *   models/networks/generator.py:313-351     SimplifiedLIP / lip2d         -> ghost_lip_pool_nhwc
  *
  * Activations crossing this ABI are NHWC with an explicit channel stride `ld`
  * (elements between consecutive pixels).  Packed weight layouts are documented
@@ -260,6 +263,22 @@ int ghost_nhwc_to_nchw(int dtype, const void* x, int ldx, int B, int H, int W, i
 /* transform_target_to_torch (core.py:13-26): uint8 BGR NHWC crops -> RGB NHWC in [-1,1] (dtype f32/bf16) */
 int ghost_crops_to_input_nhwc(const uint8_t* crops, int64_t crop_batch_stride, int B, int H, int W, int dtype, void* y,
                               void* stream);
+/* ---- use_sr face enhancer (LIPSPADEGenerator; inference.py:42-50, models/networks/generator.py:353-388,
+ *      models/networks/normalization.py:63-107): the two passes its convs do not cover ---------------------
+ * out[b,y,x,c] = act((src - mean) * rstd * gamma + beta), act(v) = v > 0 ? v : v * slope (0: ReLU, 1: none).
+ * stat = [Bs][C][2] (mean, rstd) in ghost_instnorm_stats_nhwc's layout: Bs = B per-sample (InstanceNorm), Bs = 1
+ * one record for the whole batch (train-mode BatchNorm: ghost_instnorm_stats_nhwc with B = 1, HW = B*H*W).
+ * gb (optional, NULL: gamma = 1, beta = 0): one [B,H,W,ldgb] tensor of dtype holding gamma at channel c and beta
+ * at C + c.  up2x = 1: src is [B,H/2,W/2,C] and is read at (y >> 1, x >> 1) (nearest x2 folded into the read; stat
+ * is that of the small tensor).  GHOST_EINVAL: C % 8 != 0, odd H or W with up2x, a null src / stat / out, Bs not in
+ * {1, B}, or a leading dimension / pointer that is not 16-byte aligned. */
+int ghost_norm_modulate_nhwc(int dtype, const void* src, int ldx, int B, int H, int W, int C, const float* stat, int Bs,
+                             const void* gb, int ldgb, float slope, int up2x, void* out, int ldo, void* stream);
+/* SimplifiedLIP pooling: out[B,H/2,W/2,C] = sum3x3 x e^l / sum3x3 e^l over the 3x3 / stride 2 / pad 1 window
+ * (out-of-image taps skipped), l = 12 sigmoid(((logit_raw - mean) * rstd) * w[c] + b[c]); stat = [B][C][2] instance
+ * statistics of logit_raw.  GHOST_EINVAL: odd H or W, C % 8 != 0, null pointers, misaligned leading dimensions. */
+int ghost_lip_pool_nhwc(int dtype, const void* x, int ldx, const void* logit_raw, int ldl, int B, int H, int W, int C,
+                        const float* stat, const float* w, const float* b, void* out, int ldo, void* stream);
 /* ---- ArcFace identity encoder (IResNet, the netArc GHOST loads) ------------------------
  * Replaces: inference.py:33-36 iresnet100(fp16=False) + load_state_dict + .cuda().eval();
  *   core.py:43-54 / video_processing.py:136-140 netArc(F.interpolate(normalize_and_torch_batch(crops),
