@@ -106,6 +106,7 @@ _SIGS = {
     "ghost_plan_log": (i32, [i32]),
     "ghost_plan_log_read": (i64, [C.c_char_p, i64]),
     "ghost_aad_plan": (i64, [i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, C.POINTER(i32), C.c_char_p, i64]),
+    "ghost_conv_plan": (i64, [i32] * 22 + [C.POINTER(i64), C.c_char_p, i64]),
 }
 
 

@@ -23,6 +23,7 @@
 #include "aad_wide.h"
 #include "conv_igemm.h"
 #include "conv_narrow.h"
+#include "conv_path.h"
 #include "ghost_common.h"
 #include "ops.h"
 #include "tap_rows.h"
@@ -1631,6 +1632,56 @@ extern "C" int64_t ghost_aad_plan(int dtype, int B, int H, int W, int C, int Ca,
   if (!sig.s[0]) return fail(GHOST_EINVAL, "aad_plan: no aad_v3 / aad_wide kernel takes this shape");
   if (cap > 0) snprintf(buf, (size_t)cap, "%s", sig.s);
   return (int64_t)strlen(sig.s) + 1;
+}
+
+extern "C" int64_t ghost_conv_plan(int ti, int to, int kind, int B, int H, int W, int Cin, int ldx, int N, int Npad,
+                                   int Kpad, int kh, int kw, int stride, int pad, int ldy, int epi, int split_k,
+                                   int min_wgs, int nsem, int ncu, int flags, int64_t* ws_bytes, char* buf, int64_t cap) {
+  if ((kind != CONV_FWD && kind != CONV_T4S2) || (epi != EPI_STD && epi != EPI_AAD) || split_k < 0 || nsem < 0 ||
+      ncu < 1 || (flags & ~GHOST_CONV_PLAN_FLAGS) || cap < 0 || (cap > 0 && !buf))
+    return fail(GHOST_EINVAL, "conv_plan: bad argument");
+  alignas(16) static char mem[16];   // stands for every pointer: the planners ask only whether one is set and aligned
+  float* const fp = reinterpret_cast<float*>(mem);
+  ConvDesc d;
+  d.ti = ti; d.to = to; d.kind = kind;
+  d.x = mem; d.B = B; d.Hi = H; d.Wi = W; d.Cin = Cin; d.ldx = ldx;
+  d.w = mem; d.N = N; d.Npad = Npad; d.Kpad = Kpad;
+  d.kh = kh; d.kw = kw; d.stride = stride; d.pad = pad;
+  d.y = mem; d.ldy = ldy; d.scale = fp; d.shift = fp;
+  d.epi = epi; d.force_split = split_k; d.min_wgs = min_wgs;
+  if (nsem) { d.sem = reinterpret_cast<unsigned*>(mem); d.nsem = nsem; }
+  if (epi == EPI_AAD) { d.C_aad = N / 2; d.hin = mem; d.ldh = N / 2; d.stat = d.idgb = d.mask = fp; d.id_ld = N; }
+  if (flags & GHOST_CONV_PLAN_RES) { d.res = mem; d.ldres = ldy; }
+  d.res_first = (flags & GHOST_CONV_PLAN_RES_FIRST) != 0;
+  if (flags & GHOST_CONV_PLAN_PRELU) d.prelu = fp;
+  if (flags & GHOST_CONV_PLAN_Y2) { d.y2 = mem; d.ldy2 = ldy; d.scale2 = d.shift2 = fp; }
+  if (flags & GHOST_CONV_PLAN_U8) d.u8 = reinterpret_cast<uint8_t*>(mem);
+  d.tanh_out = (flags & GHOST_CONV_PLAN_TANH) != 0;
+  if (flags & GHOST_CONV_PLAN_IN_PART) d.in_part = fp;
+  if (!conv_desc_ok(d)) return fail(GHOST_EINVAL, "conv_plan: conv_launch rejects this descriptor");
+  std::string text;
+  switch (conv_path(d)) {
+    case ConvPath::Halo3x3: {
+      const HaloPlan p = halo_plan(d, ncu);
+      if (d.in_part && !p.stats) return fail(GHOST_EINVAL, "conv_plan: this halo plan writes no InstanceNorm partials");
+      text = halo_signature(p, d).s;
+      break;
+    }
+    case ConvPath::First: text = conv_first_signature(d).s; break;
+    case ConvPath::Stem3x3: text = conv_stem3x3_signature(d).s; break;
+    case ConvPath::ConvTHalo: text = convT_halo_signature(d).s; break;
+    case ConvPath::S2Patch: text = conv_s2_patch_signature(d).s; break;
+    case ConvPath::Igemm: {
+      const IgemmPlan p = igemm_plan(d);
+      if (p.kernel == IgemmKernel::None) return fail(GHOST_EINVAL, "conv_plan: no implicit-GEMM instance takes this descriptor");
+      text = igemm_signature(p, d).s;
+      if (p.reduce != IgemmReduce::None) text += std::string("\n") + igemm_reduce_signature(p, d).s;
+      break;
+    }
+  }
+  if (ws_bytes) *ws_bytes = (int64_t)conv_workspace_bytes(d);
+  if (cap > 0) snprintf(buf, (size_t)cap, "%s", text.c_str());
+  return (int64_t)text.size() + 1;
 }
 
 extern "C" int ghost_aad_mask_nhwc(int dtype, const void* h, int ldh, int B, int HW, int C, float* stat, const float* wh0,

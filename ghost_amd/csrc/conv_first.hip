@@ -186,16 +186,31 @@ bool conv_first_supported(const ConvDesc& d) {
 
 size_t conv_first_workspace_bytes() { return 32 * 48 * sizeof(float); }
 
+bool conv_first_mfma(const ConvDesc& d) {
+  const int Wo = (d.Wi + 2 - 4) / 2 + 1;
+  return is16(d.ti) && d.ldx == 4 && Wo % 64 == 0 && d.ldy % 4 == 0 && (uintptr_t)d.x % 8 == 0;
+}
+
+PlanSig conv_first_signature(const ConvDesc& d) {
+  const long M = (long)d.B * ((d.Hi + 2 - 4) / 2 + 1) * ((d.Wi + 2 - 4) / 2 + 1);
+  PlanSig g;
+  if (conv_first_mfma(d))
+    snprintf(g.s, sizeof(g.s), "first mfma t=%s chunktail=%d", plan_dt(d.ti), (M / 64) % (4 * kFirstChunks) != 0);
+  else
+    snprintf(g.s, sizeof(g.s), "first scalar t=%s mtail=%d", plan_dt(d.ti), M % 256 != 0);
+  return g;
+}
+
 int conv_first(const ConvDesc& d, void* ws, size_t ws_bytes, hipStream_t s) {
   if (!conv_first_supported(d)) return -1;
   const int Ho = (d.Hi + 2 - 4) / 2 + 1, Wo = (d.Wi + 2 - 4) / 2 + 1;
-  if (is16(d.ti) && d.ldx == 4 && Wo % 64 == 0 && d.ldy % 4 == 0 && (uintptr_t)d.x % 8 == 0) {
+  if (conv_first_mfma(d)) {
     FirstMfmaArgs m{};
     m.x = d.x; m.w = d.w; m.y = d.y; m.scale = d.scale; m.shift = d.shift;
     m.Hi = d.Hi; m.Wi = d.Wi; m.Ho = Ho; m.Wo = Wo; m.Kpad = d.Kpad; m.ldy = d.ldy; m.slope = d.slope;
     m.M = (long)d.B * Ho * Wo;
     const dim3 g((unsigned)(((m.M / 64 + kFirstChunks - 1) / kFirstChunks + 3) / 4));
-    GHOST_PLAN_LOG("first mfma t=%s chunktail=%d", plan_dt(d.ti), (m.M / 64) % (4 * kFirstChunks) != 0);
+    GHOST_PLAN_LOG("%s", conv_first_signature(d).s);
     if (d.ti == GHOST_BF16)
       hipLaunchKernelGGL(conv_first_mfma_kernel<bf16>, g, dim3(256), 0, s, m);
     else
@@ -218,7 +233,7 @@ int conv_first(const ConvDesc& d, void* ws, size_t ws_bytes, hipStream_t s) {
   a.Kpad = d.Kpad; a.ldy = d.ldy; a.slope = d.slope;
   a.M = (long)d.B * a.Ho * a.Wo;
   dim3 grid((unsigned)((a.M + 255) / 256));
-  GHOST_PLAN_LOG("first scalar t=%s mtail=%d", plan_dt(d.ti), a.M % 256 != 0);
+  GHOST_PLAN_LOG("%s", conv_first_signature(d).s);
   if (d.ti == GHOST_BF16)
     hipLaunchKernelGGL((conv_first_kernel<bf16, 32>), grid, dim3(256), 0, s, a);
   else if (d.ti == GHOST_F16)
@@ -371,6 +386,14 @@ bool conv_stem3x3_supported(const ConvDesc& d) {
          (!d.y2 || (d.scale2 && d.shift2 && d.ldy2 % 4 == 0 && (uintptr_t)d.y2 % 8 == 0));
 }
 
+PlanSig conv_stem3x3_signature(const ConvDesc& d) {
+  const int M = d.B * d.Hi * d.Wi;
+  PlanSig g;
+  snprintf(g.s, sizeof(g.s), "stem3x3 t=bf16 y2=%d mtail=%d chunktail=%d", d.y2 != nullptr, M % 64 != 0,
+           ((M + 63) / 64) % (4 * kStemChunks) != 0);
+  return g;
+}
+
 int conv_stem3x3(const ConvDesc& d, hipStream_t s) {
   if (!conv_stem3x3_supported(d)) return -1;
   StemArgs a{};
@@ -379,8 +402,7 @@ int conv_stem3x3(const ConvDesc& d, hipStream_t s) {
   a.H = d.Hi; a.W = d.Wi; a.Kpad = d.Kpad; a.ldy = d.ldy; a.ldy2 = d.ldy2; a.slope = d.slope;
   a.M = d.B * d.Hi * d.Wi;
   const long waves = ((long)(a.M + 63) / 64 + kStemChunks - 1) / kStemChunks;
-  GHOST_PLAN_LOG("stem3x3 t=bf16 y2=%d mtail=%d chunktail=%d", d.y2 != nullptr, a.M % 64 != 0,
-                 ((a.M + 63) / 64) % (4 * kStemChunks) != 0);
+  GHOST_PLAN_LOG("%s", conv_stem3x3_signature(d).s);
   hipLaunchKernelGGL(conv_stem3x3_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }

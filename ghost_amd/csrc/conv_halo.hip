@@ -16,6 +16,7 @@
 // that may overhang 112/56/28/14-pixel images: the halo DMA zero-fills outside the image and the
 // epilogue drops those pixels; it also applies the IBasicBlock epilogue (PReLU, residual, the next
 // block's BatchNorm as a second output).
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -56,10 +57,6 @@ using HaloWide = HaloCfg<16, 32, 8, 1>;    // W % 32 == 0: 16 x 32 tile, 8 waves
 using HaloSmall = HaloCfg<16, 16, 4, 1>;   // W == 16: 16 x 16 tile, 4 waves, 57 KB LDS
 using HaloImg8 = HaloCfg<8, 8, 4, 1, 4>;   // 8 x 8 images, four per tile, 4 waves, 61 KB per stage
 using HaloPair = HaloCfg<16, 16, 8, 1, 2>; // a 16 x 16 window of two samples, 8 waves, 77 KB per stage
-// the configuration's name in the plan log
-template <class G> static const char* halo_cfg_name() {
-  return G::IMG == 4 ? "Img8" : G::IMG == 2 ? "Pair" : G::TW == 32 ? "Wide" : "Small";
-}
 
 struct HaloArgs {
   const void* x;   // 16-bit storage (bf16 or fp16: the kernels' T)
@@ -1030,6 +1027,13 @@ bool convT_halo_supported(const ConvDesc& d) {
   return (long)d.Hi * d.Wi * d.ldx < (1L << 31);
 }
 
+PlanSig convT_halo_signature(const ConvDesc& d) {
+  PlanSig g;
+  snprintf(g.s, sizeof(g.s), "convT_halo t=%s BN=%d Cin=%d N=%d res=%d", plan_dt(d.ti), d.N == 32 ? 32 : 64, d.Cin, d.N,
+           d.res != nullptr);
+  return g;
+}
+
 template <typename T, int BN>
 static int haloT_launch(const ConvDesc& d, hipStream_t s) {
   HaloTArgs a{};
@@ -1040,7 +1044,7 @@ static int haloT_launch(const ConvDesc& d, hipStream_t s) {
   a.ldy = d.ldy; a.ldres = d.ldres; a.slope = d.slope;
   a.tiles_x = d.Wi / HaloTCfg<BN>::TIW; a.tiles_y = d.Hi / HaloTCfg<BN>::TIH; a.nNt = (d.N + BN - 1) / BN;
   const long ntiles = (long)d.B * a.tiles_x * a.tiles_y * a.nNt;
-  GHOST_PLAN_LOG("convT_halo t=%s BN=%d Cin=%d N=%d res=%d", plan_dt(gdt<T>()), BN, d.Cin, d.N, d.res != nullptr);
+  GHOST_PLAN_LOG("%s", convT_halo_signature(d).s);
   hipLaunchKernelGGL((convT_halo_kernel<T, BN>), dim3((unsigned)ntiles), dim3(512), 0, s, a);
   return (int)hipGetLastError();
 }
@@ -1051,66 +1055,152 @@ int convT_halo(const ConvDesc& d, hipStream_t s) {
   return d.N == 32 ? haloT_launch<bf16, 32>(d, s) : haloT_launch<bf16, 64>(d, s);
 }
 
-// which tile the non-persistent kernel uses: 16 x 32 when the image is a multiple of it (every
-// generator stage from 32x32 up), else 16 x 16 tiles allowed to overhang the image by up to a
-// quarter of the work (ArcFace 112 / 56 / 28 / 14: 100 / 77 / 77 / 77 % of the tile pixels used;
-// 7x7 and the generator's 8x8 and below stay on the implicit GEMM)
-static bool halo_exact_wide(const ConvDesc& d) { return d.Wi % HaloWide::TW == 0 && d.Hi % HaloWide::TH == 0; }
-// the 8 x 8 stage: four whole images per tile (HaloImg8)
-static bool halo_img8(const ConvDesc& d) {
-  static const int on = GHOST_KNOB("GHOST_HALO_IMG8", 1);
-  const int ncb = d.Cin / 32;
-  // (only shapes the persistent IMG8 kernel is instantiated for, with its 16-byte stores: anything else
-  // falls through to the implicit GEMM instead of failing in conv3x3_halo)
-  return on && d.Hi == HaloImg8::TH && d.Wi == HaloImg8::TW && d.B % HaloImg8::IMG == 0 && d.N <= 1024 &&
-         !d.prelu && !d.y2 && !d.res_first && !d.tanh_out && d.Cin % 64 == 0 && d.Cin <= 1024 &&
-         (ncb == 2 || ncb == 4 || ncb == 8 || ncb == 16 || ncb == 32) && d.ldy % 8 == 0 && (uintptr_t)d.y % 16 == 0;
-}
-static bool halo_small_ok(const ConvDesc& d) {
-  const long tx = (d.Wi + HaloSmall::TW - 1) / HaloSmall::TW, ty = (d.Hi + HaloSmall::TH - 1) / HaloSmall::TH;
-  return 4L * d.Hi * d.Wi >= 3L * tx * ty * HaloSmall::TW * HaloSmall::TH;
-}
+// ---------------------------------------------------------------------------
+// host side of the 3x3 family: halo_plan decides (kernel, tile, template flags, grid) from the descriptor's integers
+// and the CU count; conv3x3_halo launches the plan's row of the one table of instantiations
+// ---------------------------------------------------------------------------
+// the tiles' geometry, indexed by HaloTile
+struct HaloGeom { int TH, TW, IMG, NW; const char* name; };
+template <class G> static constexpr HaloGeom halo_geom(const char* name) { return {G::TH, G::TW, G::IMG, G::NW, name}; }
+static constexpr HaloGeom kHaloGeom[] = {halo_geom<HaloWide>("Wide"), halo_geom<HaloSmall>("Small"),
+                                         halo_geom<HaloImg8>("Img8"), halo_geom<HaloPair>("Pair")};
 
-bool conv3x3_halo_supported(const ConvDesc& d) {
+HaloPlan halo_plan(const ConvDesc& d, int ncu) {
+  HaloPlan p;
   static const int enabled = GHOST_KNOB("GHOST_CONV_HALO", 1);
-  if (!enabled || d.kind != CONV_FWD || d.kh != 3 || d.kw != 3 || d.stride != 1 || d.pad != 1) return false;
-  if (!is16(d.ti) || d.to != d.ti || d.epi != EPI_STD || d.u8 || d.force_split) return false;
-  if (d.Cin % 32 || d.ldx % 8 || d.N % 64 || d.ldy % 4 || (d.res && d.ldres % 4)) return false;
-  if (d.y2 && (d.ldy2 % 4 || (uintptr_t)d.y2 % 8 || !d.scale2 || !d.shift2)) return false;
-  if ((!halo_exact_wide(d) && !halo_small_ok(d) && !halo_img8(d)) || d.Kpad < 9 * d.Cin || d.Npad < d.N) return false;
-  if ((uintptr_t)d.x % 16 || (uintptr_t)d.w % 16 || (uintptr_t)d.y % 8 || (d.res && (uintptr_t)d.res % 8)) return false;
-  if ((long)d.Hi * d.Wi * d.ldx >= (1L << 31) || (long)d.Npad * d.Kpad >= (1L << 31)) return false;   // 32-bit offsets
+  if (!enabled || d.kind != CONV_FWD || d.kh != 3 || d.kw != 3 || d.stride != 1 || d.pad != 1) return p;
+  if (!is16(d.ti) || d.to != d.ti || d.epi != EPI_STD || d.u8 || d.force_split) return p;
+  if (d.Cin % 32 || d.ldx % 8 || d.N % 64 || d.ldy % 4 || (d.res && d.ldres % 4)) return p;
+  if (d.y2 && (d.ldy2 % 4 || (uintptr_t)d.y2 % 8 || !d.scale2 || !d.shift2)) return p;
+  // which tile: 16 x 32 when the image is a multiple of it (every generator stage from 32x32 up), else 16 x 16
+  // tiles allowed to overhang the image by up to a quarter of the work (ArcFace 112 / 56 / 28 / 14: 100 / 77 / 77 /
+  // 77 % of the tile pixels used; 7x7 and the generator's 4x4 and below stay on the implicit GEMM), or, at the
+  // 8 x 8 stage, four whole images per tile (only shapes the persistent Img8 kernel is instantiated for, with its
+  // 16-byte stores: anything else falls through to the implicit GEMM)
+  const bool wide = d.Wi % HaloWide::TW == 0 && d.Hi % HaloWide::TH == 0;
+  const long stx = (d.Wi + HaloSmall::TW - 1) / HaloSmall::TW, sty = (d.Hi + HaloSmall::TH - 1) / HaloSmall::TH;
+  const bool small_ok = 4L * d.Hi * d.Wi >= 3L * stx * sty * HaloSmall::TW * HaloSmall::TH;
+  const int ncb = d.Cin / 32;
+  const bool ncb_pow2 = ncb == 2 || ncb == 4 || ncb == 8 || ncb == 16 || ncb == 32;
+  const bool plain = !d.prelu && !d.y2 && !d.res_first;           // epilogue variants of the non-persistent kernel only
+  const bool w16 = d.ldy % 8 == 0 && (uintptr_t)d.y % 16 == 0;    // the 16-byte epilogue stores
+  static const int img8_on = GHOST_KNOB("GHOST_HALO_IMG8", 1);
+  const bool img8 = img8_on && d.Hi == HaloImg8::TH && d.Wi == HaloImg8::TW && d.B % HaloImg8::IMG == 0 && d.N <= 1024 &&
+                    plain && !d.tanh_out && d.Cin % 64 == 0 && d.Cin <= 1024 && ncb_pow2 && w16;
+  if ((!wide && !small_ok && !img8) || d.Kpad < 9 * d.Cin || d.Npad < d.N) return p;
+  if ((uintptr_t)d.x % 16 || (uintptr_t)d.w % 16 || (uintptr_t)d.y % 8 || (d.res && (uintptr_t)d.res % 8)) return p;
+  if ((long)d.Hi * d.Wi * d.ldx >= (1L << 31) || (long)d.Npad * d.Kpad >= (1L << 31)) return p;   // 32-bit offsets
   // a work item is one (tile, 64-channel block) with the whole 9 x Cin reduction: under 64 of them (B = 1 at 32 x 32,
   // 512 -> 512: 16 workgroups, 105 us) most CUs idle, and the implicit GEMM's split K spreads the same conv wider
-  if (!halo_img8(d)) {
-    const bool wide = halo_exact_wide(d);
+  if (!img8) {
     const int th = wide ? HaloWide::TH : HaloSmall::TH, tw = wide ? HaloWide::TW : HaloSmall::TW;
     const long items = (long)d.B * ((d.Hi + th - 1) / th) * ((d.Wi + tw - 1) / tw) * (d.N / 64);
     static const int min_items = GHOST_KNOB("GHOST_HALO_MIN_ITEMS", 64);
-    if (items < min_items) return false;
+    if (items < min_items) return p;
   }
   // measured (tools/bench_ops.py, B = 64): faster than the implicit GEMM at every generator stage
   // from 32x32 up (N = 64 .. 512); GHOST_CONV_HALO_MAXN caps N for A/B runs
   static const int max_n = GHOST_KNOB("GHOST_CONV_HALO_MAXN", 1 << 30);
-  return d.N <= max_n;
+  if (d.N > max_n) return p;
+
+  static const int pp = GHOST_KNOB("GHOST_HALO_PP", 1);
+  static const int max_cin = GHOST_KNOB("GHOST_HALO_PP_MAXCIN", 1024);
+  static const int force_small = GHOST_KNOB("GHOST_HALO_PP_SMALL", 0);
+  // measured A/B (B = 64): the persistent form wins at every generator shape with W % 32 == 0 (256x256:
+  // -23 %, 128x128: -7 %, 64x64 256->256: -9 %; with the counted first-stage wait also 64x64 512->128
+  // -11 %, 32x32 512->512 -6 %, 32x32 1024->256 -8 %: +3 % frames/s end to end)
+  const bool cin_ok = d.Cin == 64 || d.Cin == 128 || d.Cin == 192 || d.Cin == 256 || d.Cin == 512 || d.Cin == 1024;
+  if (img8) {
+    p.kernel = HaloKernel::HaloPP; p.tile = HaloTile::Img8;
+    p.nrec = 1;   // a wave's 64 pixels are one whole image
+  } else if (wide && pp && plain && w16 && d.N <= 512 && cin_ok && d.Cin <= max_cin && !d.tanh_out) {
+    p.kernel = HaloKernel::HaloPP; p.tile = HaloTile::Wide;
+    // records per sample: one per wave and tile = 64 pixels each (16 x 32 tiles x 8 waves)
+    p.nrec = (d.Hi / HaloWide::TH) * (d.Wi / HaloWide::TW) * 8;
+  } else if (pp && !wide && small_ok && (force_small || d.Wi % HaloSmall::TW || d.Hi % HaloSmall::TH || !plain) &&
+             d.N <= 512 && d.Cin % 64 == 0 && (ncb_pow2 || ncb == 6)) {
+    // the persistent kernel on 16 x 16 tiles for images that are not a multiple of 16 x 32 (ArcFace 112 .. 14,
+    // overhanging tiles) — or, with GHOST_HALO_PP_SMALL=1, also the generator's 16 x 16 stage (A/B knob; its
+    // 1024 -> 1024 and cat 2048 -> 512 convs are outside the persistent kernel's N <= 512 / NCB <= 32 anyway).
+    // Two samples per tile (Pair) when the batch pairs up: every weight stage serves both.  Measured
+    // (ArcFace iresnet100 bf16, per conv): it wins wherever the paired grid still has a work item per CU —
+    // B = 128: 14x14 51.2 -> 40.8 us, 28x28 63.9 -> 51.2, 56x56 107.7 -> 83.8; B = 64: 28x28 35.3 -> 29.2,
+    // 56x56 59.4 -> 46.6 — and loses below that (B = 64 at 14x14, 128 items: 28.8 -> 36.2 us)
+    static const int pair = GHOST_KNOB("GHOST_HALO_PAIR", 1);
+    const long pair_items = (long)(d.B / 2) * stx * sty * (d.N / 64);
+    p.kernel = HaloKernel::HaloPP;
+    p.tile = pair && d.B % 2 == 0 && d.N <= 256 && pair_items >= ncu ? HaloTile::Pair : HaloTile::Small;
+  } else {
+    p.kernel = HaloKernel::Halo;
+    p.tile = wide ? HaloTile::Wide : HaloTile::Small;
+  }
+  const HaloGeom& g = kHaloGeom[(int)p.tile];
+  p.tiles_x = (d.Wi + g.TW - 1) / g.TW; p.tiles_y = (d.Hi + g.TH - 1) / g.TH;
+  p.ntiles = d.B / g.IMG * p.tiles_x * p.tiles_y * (d.N / 64);
+  p.block = (unsigned)g.NW * 64;
+  if (p.kernel == HaloKernel::HaloPP) {
+    p.resw = d.Cin <= 64 && d.N == 64;
+    p.ncb = ncb;
+    p.stats = d.in_part && p.nrec > 0;
+    // (A/B knob, tuning build) the persistent grid as a share of the CUs: with two batches in flight the other
+    // batch's kernels can only use the CUs this kernel's 150 KB-LDS workgroups leave free
+    static const int pct = GHOST_KNOB("GHOST_PP_GRID_PCT", 100);
+    const int gcu = pct >= 100 ? ncu : (ncu * pct / 100 + 7) / 8 * 8;
+    p.grid = (unsigned)(p.ntiles < gcu ? p.ntiles : gcu);
+  } else {
+    p.grid = (unsigned)p.ntiles;
+  }
+  return p;
 }
 
-template <typename T, class G>
-static int halo_launch(const ConvDesc& d, hipStream_t s) {
-  HaloArgs a{};
-  a.x = d.x; a.w = d.w; a.y = d.y;
-  a.scale = d.scale; a.shift = d.shift; a.res = d.res;
-  a.H = d.Hi; a.W = d.Wi; a.Cin = d.Cin; a.ldx = d.ldx; a.N = d.N; a.Kpad = d.Kpad;
-  a.ldy = d.ldy; a.ldres = d.ldres; a.tanh_out = d.tanh_out; a.slope = d.slope;
-  a.prelu = d.prelu; a.y2 = d.y2; a.scale2 = d.scale2; a.shift2 = d.shift2; a.ldy2 = d.ldy2;
-  a.res_first = d.res_first;
-  a.tiles_x = (d.Wi + G::TW - 1) / G::TW; a.tiles_y = (d.Hi + G::TH - 1) / G::TH;
-  a.nNt = (d.N + G::BN - 1) / G::BN;
-  a.ntiles = d.B * a.tiles_x * a.tiles_y * a.nNt;
-  GHOST_PLAN_LOG("halo t=%s tile=%s Cin=%d N=%d overhang=%d", plan_dt(gdt<T>()), halo_cfg_name<G>(), d.Cin, d.N,
-                 d.Hi % G::TH != 0 || d.Wi % G::TW != 0);
-  hipLaunchKernelGGL((conv3x3_halo_kernel<T, G>), dim3((unsigned)a.ntiles), dim3(G::NW * 64), 0, s, a);
-  return (int)hipGetLastError();
+// the queries never depend on the CU count (halo_plan): any stands in
+bool conv3x3_halo_supported(const ConvDesc& d) { return halo_plan(d, 256).kernel != HaloKernel::None; }
+
+bool conv3x3_pp_takes(const ConvDesc& d, int* nrec) {
+  const HaloPlan p = halo_plan(d, 256);
+  if (p.nrec > 0 && nrec) *nrec = p.nrec;
+  return p.nrec > 0;
+}
+
+PlanSig halo_signature(const HaloPlan& p, const ConvDesc& d) {
+  const HaloGeom& g = kHaloGeom[(int)p.tile];
+  const int overhang = d.Hi % g.TH != 0 || d.Wi % g.TW != 0;
+  PlanSig sig;
+  if (p.kernel == HaloKernel::HaloPP)
+    snprintf(sig.s, sizeof(sig.s), "halo_pp t=%s tile=%s RESW=%d STATS=%d NCB=%d N=%d overhang=%d uneven=%d", plan_dt(d.ti),
+             g.name, (int)p.resw, (int)p.stats, p.ncb, d.N, overhang, p.ntiles % (int)p.grid != 0);
+  else
+    snprintf(sig.s, sizeof(sig.s), "halo t=%s tile=%s Cin=%d N=%d overhang=%d", plan_dt(d.ti), g.name, d.Cin, d.N, overhang);
+  return sig;
+}
+
+// every instantiation, once: (kernel, tile, RESW, STATS, NCB) -> the kernel.  The partials (STATS) come from exact
+// 16 x 32 tiles or whole 8 x 8 images only.
+typedef void (*HaloFn)(const HaloArgs);
+struct HaloRow {
+  HaloKernel kernel;
+  HaloTile tile;
+  bool resw, stats;
+  int ncb;
+  HaloFn fn;
+};
+
+template <typename T>
+static HaloFn halo_fn(const HaloPlan& p) {
+#define GHOST_ROW(G, r, st, nb) {HaloKernel::HaloPP, HaloTile::G, r, st, nb, conv3x3_halo_pp_kernel<T, Halo##G, r, st, nb>},
+#define GHOST_PP(G, st)                                                                             \
+  GHOST_ROW(G, true, st, 2) GHOST_ROW(G, false, st, 2) GHOST_ROW(G, false, st, 4) GHOST_ROW(G, false, st, 6) \
+  GHOST_ROW(G, false, st, 8) GHOST_ROW(G, false, st, 16) GHOST_ROW(G, false, st, 32)
+  static const HaloRow rows[] = {
+      {HaloKernel::Halo, HaloTile::Wide, false, false, 0, conv3x3_halo_kernel<T, HaloWide>},
+      {HaloKernel::Halo, HaloTile::Small, false, false, 0, conv3x3_halo_kernel<T, HaloSmall>},
+      GHOST_PP(Wide, false) GHOST_PP(Wide, true) GHOST_PP(Img8, false) GHOST_PP(Img8, true)
+      GHOST_PP(Small, false) GHOST_PP(Pair, false)};
+#undef GHOST_PP
+#undef GHOST_ROW
+  for (const HaloRow& r : rows)
+    if (r.kernel == p.kernel && r.tile == p.tile && r.resw == p.resw && r.stats == p.stats && r.ncb == p.ncb) return r.fn;
+  return nullptr;
 }
 
 static int num_cus() {
@@ -1124,17 +1214,10 @@ static int num_cus() {
   return n;
 }
 
-// the persistent kernel takes 16 x 16 tiles (HaloSmall) for images that are not a multiple of 16 x 32
-// (ArcFace 112 .. 14, overhanging tiles) — or, with GHOST_HALO_PP_SMALL=1, also the generator's 16 x 16 stage (A/B knob;
-// its 1024 -> 1024 and cat 2048 -> 512 convs are outside the persistent kernel's N <= 512 / NCB <= 32 anyway)
-static bool pp_small(const ConvDesc& d) {
-  static const int force = GHOST_KNOB("GHOST_HALO_PP_SMALL", 0);
-  return !halo_exact_wide(d) && halo_small_ok(d) &&
-         (force || d.Wi % HaloSmall::TW || d.Hi % HaloSmall::TH || d.prelu || d.y2 || d.res_first);
-}
-
-template <typename T, class G>
-static int halo_pp_launch(const ConvDesc& d, hipStream_t s) {
+template <typename T>
+static int halo_launch(const ConvDesc& d, const HaloPlan& p, hipStream_t s) {
+  const HaloFn fn = halo_fn<T>(p);
+  if (!fn) return -1;
   HaloArgs a{};
   a.x = d.x; a.w = d.w; a.y = d.y;
   a.scale = d.scale; a.shift = d.shift; a.res = d.res;
@@ -1142,24 +1225,18 @@ static int halo_pp_launch(const ConvDesc& d, hipStream_t s) {
   a.ldy = d.ldy; a.ldres = d.ldres; a.tanh_out = d.tanh_out; a.slope = d.slope;
   a.prelu = d.prelu; a.y2 = d.y2; a.scale2 = d.scale2; a.shift2 = d.shift2; a.ldy2 = d.ldy2;
   a.res_first = d.res_first;
-  a.tiles_x = (d.Wi + G::TW - 1) / G::TW; a.tiles_y = (d.Hi + G::TH - 1) / G::TH; a.nNt = d.N / 64;
-  a.ntiles = d.B / G::IMG * a.tiles_x * a.tiles_y * a.nNt;
-  static const int dbg = GHOST_KNOB("GHOST_HALO_DBG", 0);
-  a.dbg = dbg;
-  // (A/B knob, tuning build) the persistent grid as a share of the CUs: with two batches in flight the other
-  // batch's kernels can only use the CUs this kernel's 150 KB-LDS workgroups leave free
-  static const int pct = GHOST_KNOB("GHOST_PP_GRID_PCT", 100);
-  const int ncu = pct >= 100 ? num_cus() : (num_cus() * pct / 100 + 7) / 8 * 8;
-  const int g = a.ntiles < ncu ? a.ntiles : ncu;
-  a.in_part = d.in_part;
-  const bool resw = d.Cin <= 64 && d.N == 64;
-  const int ncb = d.Cin / 32;
-  constexpr int NT = G::NW * 64;
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.nNt = d.N / 64; a.ntiles = p.ntiles;
+  if (p.kernel == HaloKernel::HaloPP) {
+    static const int dbg = GHOST_KNOB("GHOST_HALO_DBG", 0);
+    a.dbg = dbg;
+    a.in_part = d.in_part;
 #ifdef GHOST_TUNING
-  if constexpr (G::TW == 32) {
-    if (dbg) {   // experiment variants, with or without the InstanceNorm partials (tuning builds only)
+    if (p.tile == HaloTile::Wide && dbg) {   // experiment variants, with or without the InstanceNorm partials (tuning builds only)
+      using G = HaloWide;
+      constexpr int NT = G::NW * 64;
+      const unsigned g = p.grid;
 #define GHOST_PP_DBX(R, NB, V)                                                                                    \
-  if (resw == R && ncb == NB && dbg == V) {                                                                      \
+  if (p.resw == R && p.ncb == NB && dbg == V) {                                                                  \
     if (a.in_part)                                                                                               \
       hipLaunchKernelGGL((conv3x3_halo_pp_kernel<T, G, R, true, NB, V>), dim3((unsigned)g), dim3(NT), 0, s, a);  \
     else                                                                                                         \
@@ -1173,87 +1250,18 @@ static int halo_pp_launch(const ConvDesc& d, hipStream_t s) {
       GHOST_PP_DBX(false, 16, 4096) GHOST_PP_DBX(false, 32, 4096)
 #undef GHOST_PP_DBX
     }
-  }
 #endif
-  constexpr bool CAN_ST = G::TW != 16;   // the partials come from exact 16 x 32 tiles or whole 8 x 8 images
-#define GHOST_PP(R, ST, NB)                                                                                       \
-  GHOST_PLAN_LOG("halo_pp t=%s tile=%s RESW=%d STATS=%d NCB=%d N=%d overhang=%d uneven=%d", plan_dt(gdt<T>()),    \
-                 halo_cfg_name<G>(), (int)R, (int)ST, NB, d.N, d.Hi % G::TH != 0 || d.Wi % G::TW != 0,            \
-                 a.ntiles % g != 0);                                                                              \
-  hipLaunchKernelGGL((conv3x3_halo_pp_kernel<T, G, R, ST, NB>), dim3((unsigned)g), dim3(NT), 0, s, a)
-#define GHOST_PP2(R, NB)                                  \
-  if constexpr (CAN_ST) {                                  \
-    if (a.in_part) { GHOST_PP(R, CAN_ST, NB); } else { GHOST_PP(R, false, NB); } \
-  } else {                                                 \
-    if (a.in_part) return -1;                              \
-    GHOST_PP(R, false, NB);                                \
   }
-  if (resw) {
-    GHOST_PP2(true, 2)
-  } else {
-    switch (ncb) {
-      case 2: GHOST_PP2(false, 2) break;
-      case 4: GHOST_PP2(false, 4) break;
-      case 6: GHOST_PP2(false, 6) break;
-      case 8: GHOST_PP2(false, 8) break;
-      case 16: GHOST_PP2(false, 16) break;
-      case 32: GHOST_PP2(false, 32) break;
-      default: return -1;
-    }
-  }
-#undef GHOST_PP2
-#undef GHOST_PP
+  GHOST_PLAN_LOG("%s", halo_signature(p, d).s);
+  hipLaunchKernelGGL(fn, dim3(p.grid), dim3(p.block), 0, s, a);
   return (int)hipGetLastError();
 }
 
-bool conv3x3_pp_takes(const ConvDesc& d, int* nrec) {
-  static const int pp = GHOST_KNOB("GHOST_HALO_PP", 1);
-  if (!conv3x3_halo_supported(d)) return false;
-  if (d.prelu || d.y2 || d.res_first) return false;   // epilogue variants of the non-persistent kernel only
-  if (d.ldy % 8 || (uintptr_t)d.y % 16) return false;   // the 16-byte epilogue stores (W16)
-  if (halo_img8(d)) {
-    const int ncb = d.Cin / 32;
-    const bool ok8 = ncb == 2 || ncb == 4 || ncb == 8 || ncb == 16 || ncb == 32;
-    if (ok8 && nrec) *nrec = 1;   // a wave's 64 pixels are one whole image
-    return ok8;
-  }
-  const bool wide = halo_exact_wide(d);
-  static const int max_cin = GHOST_KNOB("GHOST_HALO_PP_MAXCIN", 1024);
-  // measured A/B (B = 64): the persistent form wins at every generator shape with W % 32 == 0 (256x256:
-  // -23 %, 128x128: -7 %, 64x64 256->256: -9 %; with the counted first-stage wait also 64x64 512->128
-  // -11 %, 32x32 512->512 -6 %, 32x32 1024->256 -8 %: +3 % frames/s end to end)
-  const bool cin_ok = d.Cin == 64 || d.Cin == 128 || d.Cin == 192 || d.Cin == 256 || d.Cin == 512 || d.Cin == 1024;
-  const bool ok = wide && pp && d.N <= 512 && d.N % 64 == 0 && cin_ok && d.Cin <= max_cin && !d.tanh_out;
-  // records per sample: one per wave and tile = 64 pixels each (16 x 32 tiles x 8 waves)
-  if (ok && nrec) *nrec = (d.Hi / HaloWide::TH) * (d.Wi / HaloWide::TW) * 8;
-  return ok;
-}
-
-template <typename T>
-static int conv3x3_halo_t(const ConvDesc& d, hipStream_t s) {
-  if (halo_img8(d)) return conv3x3_pp_takes(d, nullptr) ? halo_pp_launch<T, HaloImg8>(d, s) : -1;
-  if (conv3x3_pp_takes(d, nullptr)) return halo_pp_launch<T, HaloWide>(d, s);
-  if (d.in_part) return -1;   // only the persistent 16 x 32 kernel writes InstanceNorm partials
-  static const int pp = GHOST_KNOB("GHOST_HALO_PP", 1);
-  const int ncb = d.Cin / 32;
-  if (pp && pp_small(d) && d.N <= 512 && d.Cin % 64 == 0 &&
-      (ncb == 2 || ncb == 4 || ncb == 6 || ncb == 8 || ncb == 16 || ncb == 32)) {
-    // two samples per tile (HaloPair) when the batch pairs up: every weight stage serves both.  Measured
-    // (ArcFace iresnet100 bf16, per conv): it wins wherever the paired grid still has a work item per CU —
-    // B = 128: 14x14 51.2 -> 40.8 us, 28x28 63.9 -> 51.2, 56x56 107.7 -> 83.8; B = 64: 28x28 35.3 -> 29.2,
-    // 56x56 59.4 -> 46.6 — and loses below that (B = 64 at 14x14, 128 items: 28.8 -> 36.2 us)
-    static const int pair = GHOST_KNOB("GHOST_HALO_PAIR", 1);
-    const long pair_items = (long)(d.B / 2) * ((d.Wi + 15) / 16) * ((d.Hi + 15) / 16) * (d.N / 64);
-    if (pair && d.B % 2 == 0 && d.N <= 256 && pair_items >= num_cus()) return halo_pp_launch<T, HaloPair>(d, s);
-    return halo_pp_launch<T, HaloSmall>(d, s);
-  }
-  if (halo_exact_wide(d)) return halo_launch<T, HaloWide>(d, s);
-  return halo_launch<T, HaloSmall>(d, s);
-}
-
 int conv3x3_halo(const ConvDesc& d, hipStream_t s) {
-  if (!conv3x3_halo_supported(d)) return -1;
-  return d.ti == GHOST_F16 ? conv3x3_halo_t<_Float16>(d, s) : conv3x3_halo_t<bf16>(d, s);
+  const HaloPlan p = halo_plan(d, num_cus());
+  // only the persistent 16 x 32 and 8 x 8 kernels write InstanceNorm partials
+  if (p.kernel == HaloKernel::None || (d.in_part && !p.stats)) return -1;
+  return d.ti == GHOST_F16 ? halo_launch<_Float16>(d, p, s) : halo_launch<bf16>(d, p, s);
 }
 
 }  // namespace ghost

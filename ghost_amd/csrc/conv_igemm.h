@@ -12,6 +12,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "plan_log.h"
+
 namespace ghost {
 
 enum ConvKind { CONV_FWD = 0, CONV_T4S2 = 1 };
@@ -66,6 +68,38 @@ struct ConvDesc {
   int nsem = 0;
 };
 
+// ---- the implicit GEMM's plan: everything its launch needs, decided once from the descriptor ----
+struct ConvArgs;                                  // the kernels' argument block (conv_igemm.hip)
+typedef void (*ConvKernelFn)(const ConvArgs);
+
+enum class IgemmKernel { None, Igemm, Glds };     // the register-staged tile kernel, the LDS-DMA ring kernel
+enum class IgemmReduce { None, Reduce, Reduce4, F32From16 };   // the kernel after a GEMM that wrote fp32 partials
+
+struct IgemmPlan {
+  IgemmKernel kernel = IgemmKernel::None;         // None: no instance takes the descriptor (conv_launch returns -1)
+  int BM = 0, BN = 0, BK = 0;
+  int stages = 0, wsl = 0;                        // Glds: ring stages, warp-specialised DMA waves (0 or 4)
+  bool fast = false;                              // 32-deep K slices are contiguous 16-byte-aligned runs
+  bool deep = false;                              // the deep ring (low-resolution GEMMs): one workgroup per CU
+  int to = 0;                                     // output type of the GEMM kernel (the operand type under F32From16)
+  int kepi = 0;                                   // the GEMM kernel's epilogue: 0 STD, 1 AAD, 2 SPLIT (fp32 partials)
+  int npar = 0, nMt = 0, nNt = 0, NT = 0, M = 0, Ho = 0, Wo = 0;
+  int nsplit = 0, kt_per_split = 0;
+  bool partial = false;                           // the GEMM writes fp32 partials into the workspace
+  IgemmReduce reduce = IgemmReduce::None;
+  int fixup = 0;                                  // split-K fix-up in the GEMM: 0 none, 1 standard, 2 AAD epilogue
+  unsigned grid[3] = {0, 0, 0}, block = 0, reduce_grid = 0;
+  size_t ws_bytes = 0;
+  ConvKernelFn fn = nullptr, reduce_fn = nullptr;   // the rows of the instance tables the plan selected
+};
+
+// pure: reads the descriptor's integers and flags, which pointers are set and their alignment; no HIP call
+IgemmPlan igemm_plan(const ConvDesc& d);
+PlanSig igemm_signature(const IgemmPlan& p, const ConvDesc& d);          // the GEMM's plan-log line
+PlanSig igemm_reduce_signature(const IgemmPlan& p, const ConvDesc& d);   // the reduction's (p.reduce != None)
+
+// what conv_launch asks of any descriptor before it picks a family
+bool conv_desc_ok(const ConvDesc& d);
 // bytes of fp32 split-K workspace the launch may use
 size_t conv_workspace_bytes(const ConvDesc& d);
 // returns 0 on success, else a hipError_t / -1 (bad descriptor)

@@ -15,6 +15,7 @@
 #include "plan_log.h"
 #include "conv_first.h"
 #include "conv_halo.h"
+#include "conv_path.h"
 #include "conv_s2.h"
 #include "ghost_common.h"
 
@@ -475,22 +476,6 @@ __global__ void __launch_bounds__(256) splitk_reduce4_kernel(const ConvArgs a) {
   }
 }
 
-// one reduction launch for a split-K GEMM's partials: the four-channel form when the columns allow it
-template <typename TO, int EPI>
-void launch_reduce(const ConvArgs& a, int ncols, int npar, hipStream_t s) {
-  static const int vec = GHOST_KNOB("GHOST_SPLITK_VEC", 1);
-  const long total = (long)a.M * ncols;
-  if (vec && ncols % 4 == 0 && a.NT % 4 == 0) {
-    dim3 grid((unsigned)((total / 4 + 255) / 256), 1, npar);
-    GHOST_PLAN_LOG("splitk_reduce4 to=%s epi=%s", plan_dt(gdt<TO>()), kepi_name(EPI));
-    hipLaunchKernelGGL((splitk_reduce4_kernel<TO, EPI>), grid, dim3(256), 0, s, a);
-  } else {
-    dim3 grid((unsigned)((total + 255) / 256), 1, npar);
-    GHOST_PLAN_LOG("splitk_reduce to=%s epi=%s", plan_dt(gdt<TO>()), kepi_name(EPI));
-    hipLaunchKernelGGL((splitk_reduce_kernel<TO, EPI>), grid, dim3(256), 0, s, a);
-  }
-}
-
 // ---------------------------------------------------------------------------
 // v2: bf16 implicit GEMM staged by LDS-DMA (global_load_lds_dwordx4) through a STAGES-deep
 // ring with counted vmcnt waits and raw barriers (cdna_hip_programming.md §5 "Pipelining
@@ -712,21 +697,83 @@ __global__ void __launch_bounds__(WSL ? 512 : 256) conv_glds_kernel(const ConvAr
 }
 
 // ---------------------------------------------------------------------------
-// host side: tile choice, split-K heuristic, dispatch
+// host side: igemm_plan decides tile, split-K, kernel, fix-up, reduction, grid and workspace from the descriptor's
+// integers; conv_launch picks the family (conv_path.h) and launches the plan's rows of the instance tables
 // ---------------------------------------------------------------------------
 namespace {
 
-struct Plan {
-  int BM, BN, BK, nNt, nMt, npar, nsplit, kt_per_split, NT, M, Ho, Wo;
-  bool fast;
-  bool partial;   // GEMM writes fp32 partials, splitk_reduce_kernel applies the epilogue
-  int stages;     // > 0: the LDS-DMA ring kernel with this many stages (deep ring, low-resolution GEMMs)
-};
+// every instantiation, once: (types, tile, epilogue, ...) -> the kernel
+struct IgemmRow { int ti, to, BM, BN, BK, epi; bool fast; ConvKernelFn fn; };
+struct GldsRow { int t, BM, BN, stages, epi, wsl; ConvKernelFn fn; };
+struct ReduceRow { int to, epi; bool vec4; ConvKernelFn fn; };
 
+ConvKernelFn igemm_fn(int ti, int to, int BM, int BN, int BK, int epi, bool fast) {
+#define GHOST_ROW(TI, TO, bm, bn, bk, e, f) {gdt<TI>(), gdt<TO>(), bm, bn, bk, e, f, conv_igemm_kernel<TI, TO, bm, bn, bk, e, f>},
+#define GHOST_SLOW(TI, TO, e) GHOST_ROW(TI, TO, 256, 32, 32, e, false) GHOST_ROW(TI, TO, 64, 64, 32, e, false)
+#define GHOST_AADT(TI, TO, bk) GHOST_ROW(TI, TO, 128, 128, bk, KEPI_AAD, true) GHOST_ROW(TI, TO, 64, 128, bk, KEPI_AAD, true)
+#define GHOST_SET(TI, TO, bk, e)                                                                        \
+  GHOST_ROW(TI, TO, 128, 128, bk, e, true) GHOST_ROW(TI, TO, 64, 128, bk, e, true)                          \
+  GHOST_ROW(TI, TO, 256, 64, bk, e, true) GHOST_ROW(TI, TO, 256, 32, bk, e, true) GHOST_ROW(TI, TO, 256, 16, bk, e, true)
+#define GHOST_SET16(T, e)                                                                               \
+  GHOST_SET(T, T, 32, e) GHOST_SET(T, T, 64, e) GHOST_ROW(T, T, 128, 64, 32, e, true)                   \
+  GHOST_ROW(T, T, 128, 64, 64, e, true) GHOST_ROW(T, T, 64, 64, 32, e, true) GHOST_ROW(T, T, 64, 64, 64, e, true) \
+  GHOST_ROW(T, T, 128, 32, 32, e, true) GHOST_ROW(T, T, 128, 16, 32, e, true)
+#define GHOST_T16(T)                                                                                      \
+  GHOST_SET16(T, KEPI_STD) GHOST_SET16(T, KEPI_SPLIT) GHOST_AADT(T, T, 32) GHOST_AADT(T, T, 64)         \
+  GHOST_SLOW(T, T, KEPI_STD) GHOST_SLOW(T, T, KEPI_SPLIT)
+#define GHOST_T32(TO)                                                                                     \
+  GHOST_SET(float, TO, 32, KEPI_STD) GHOST_SET(float, TO, 32, KEPI_SPLIT) GHOST_AADT(float, TO, 32)     \
+  GHOST_SLOW(float, TO, KEPI_STD) GHOST_SLOW(float, TO, KEPI_SPLIT)
+  static const IgemmRow rows[] = {GHOST_T16(bf16) GHOST_T16(_Float16) GHOST_T32(float) GHOST_T32(bf16) GHOST_T32(_Float16)};
+#undef GHOST_T32
+#undef GHOST_T16
+#undef GHOST_SET16
+#undef GHOST_SET
+#undef GHOST_AADT
+#undef GHOST_SLOW
+#undef GHOST_ROW
+  for (const IgemmRow& r : rows)
+    if (r.ti == ti && r.to == to && r.BM == BM && r.BN == BN && r.BK == BK && r.epi == epi && r.fast == fast) return r.fn;
+  return nullptr;
+}
 
-Plan make_plan(const ConvDesc& d) {
+// the LDS-DMA ring (16-bit operands and output): with the DMA waves (wsl 4, 512 threads) or without; the AAD
+// epilogue only on 128 x 128 tiles
+ConvKernelFn glds_fn(int t, int BM, int BN, int stages, int epi, int wsl) {
+#define GHOST_ROW(T, bm, bn, st, e, w) {gdt<T>(), bm, bn, st, e, w, conv_glds_kernel<T, bm, bn, st, e, w>},
+#define GHOST_G(T, bm, bn, st, e) GHOST_ROW(T, bm, bn, st, e, 4) GHOST_ROW(T, bm, bn, st, e, 0)
+#define GHOST_RING(T, e)                                                                                   \
+  GHOST_G(T, 128, 128, 8, e) GHOST_G(T, 128, 128, 6, e) GHOST_G(T, 128, 128, 4, e) GHOST_G(T, 256, 64, 4, e) \
+  GHOST_G(T, 128, 64, 4, e) GHOST_G(T, 64, 128, 4, e) GHOST_G(T, 128, 128, 3, e) GHOST_G(T, 256, 64, 3, e)   \
+  GHOST_G(T, 128, 64, 3, e) GHOST_G(T, 64, 128, 3, e)
+#define GHOST_T(T) \
+  GHOST_RING(T, KEPI_STD) GHOST_RING(T, KEPI_SPLIT) GHOST_G(T, 128, 128, 8, KEPI_AAD) GHOST_ROW(T, 128, 128, 3, KEPI_AAD, 4)
+  static const GldsRow rows[] = {GHOST_T(bf16) GHOST_T(_Float16)};
+#undef GHOST_T
+#undef GHOST_RING
+#undef GHOST_G
+#undef GHOST_ROW
+  for (const GldsRow& r : rows)
+    if (r.t == t && r.BM == BM && r.BN == BN && r.stages == stages && r.epi == epi && r.wsl == wsl) return r.fn;
+  return nullptr;
+}
+
+ConvKernelFn reduce_fn(int to, int epi, bool vec4) {
+#define GHOST_ROW(TO, e) {gdt<TO>(), e, true, splitk_reduce4_kernel<TO, e>}, {gdt<TO>(), e, false, splitk_reduce_kernel<TO, e>},
+#define GHOST_T(TO) GHOST_ROW(TO, KEPI_STD) GHOST_ROW(TO, KEPI_AAD)
+  static const ReduceRow rows[] = {GHOST_T(bf16) GHOST_T(_Float16) GHOST_T(float)};
+#undef GHOST_T
+#undef GHOST_ROW
+  for (const ReduceRow& r : rows)
+    if (r.to == to && r.epi == epi && r.vec4 == vec4) return r.fn;
+  return nullptr;
+}
+
+}  // namespace
+
+IgemmPlan igemm_plan(const ConvDesc& d) {
   static const int force_bk = GHOST_KNOB("GHOST_CONV_BK", 0);   // tuning knob (0 = heuristic)
-  Plan p{};
+  IgemmPlan p;
   p.npar = d.kind == CONV_T4S2 ? 4 : 1;
   if (d.kind == CONV_T4S2) {
     p.Ho = d.Hi;
@@ -737,19 +784,20 @@ Plan make_plan(const ConvDesc& d) {
   }
   p.M = d.B * p.Ho * p.Wo;
   const bool bf = is16(d.ti);   // 16-bit operands (bf16 or fp16)
-  const int vec = bf ? 8 : 4;
+  const int vec = bf ? 8 : 4, esz = bf ? 2 : 4;
   p.fast = (d.Cin % 32 == 0) && (d.ldx % vec == 0) && ((uintptr_t)d.x % 16 == 0);
   // BK = 64 pays only on deep reductions (measured: 256x64 tiles lose 2x at BK 64 from LDS occupancy)
   const bool bk64_ok = bf && p.fast && d.Cin % 64 == 0 && d.Kpad % 64 == 0;
   // (Kpad 4096: the encoder's 16x16 conv and 8x8 deconv, measured -10..-19 % with BK 64)
   p.BK = (bk64_ok && d.Kpad >= 4096) ? 64 : 32;
   if (force_bk == 32 || (force_bk == 64 && bk64_ok)) p.BK = force_bk;
+  const long tiles128 = (long)((p.M + 127) / 128) * ((d.N + 127) / 128) * p.npar;
   if (!p.fast) {
     p.BN = d.N <= 32 ? 32 : 64;
     p.BM = d.N <= 32 ? 256 : 64;
   } else if (d.epi == EPI_AAD) {
     p.BN = 128;
-    p.BM = ((p.M + 127) / 128) * ((d.N + 127) / 128) * p.npar >= 512 ? 128 : 64;
+    p.BM = tiles128 >= 512 ? 128 : 64;
   } else if (d.N <= 16) {
     p.BN = 16; p.BM = 256;
   } else if (d.N <= 32) {
@@ -760,7 +808,7 @@ Plan make_plan(const ConvDesc& d) {
     p.BN = 64; p.BM = (bf && d.kh == 4 && d.stride == 2 && d.kind == CONV_FWD) ? 128 : 256;
   } else {
     p.BN = 128;
-    p.BM = ((p.M + 127) / 128) * ((d.N + 127) / 128) * p.npar >= 512 ? 128 : 64;
+    p.BM = tiles128 >= 512 ? 128 : 64;
   }
   if (!p.fast || p.BM >= 256) p.BK = force_bk == 64 && bk64_ok ? 64 : 32;
   // Low-resolution GEMMs (the generator's 2x2..8x8 stages and the encoder's 16x16..2x2 convs at
@@ -771,14 +819,13 @@ Plan make_plan(const ConvDesc& d) {
   static const int deep = GHOST_KNOB("GHOST_CONV_DEEP", 8);
   // (only grids that need split-K: with >= 256 tiles of 128 x 128 the two-workgroup register-staged
   // kernel measured faster, e.g. the 8x8 AAD GEMM 55 vs 74 us)
-  const long tiles128 = (long)((p.M + 127) / 128) * ((d.N + 127) / 128) * p.npar;
   // very deep K (>= 4096: IResNet's 7 x 7 512 -> 512 convs) keeps the ring up to two rounds of workgroups:
   // at B = 256 (M = 12 544, 392 tiles) 175 -> 167 us per conv against the register-staged 64 x 128 tile (the
   // second, partial round of 136 tiles costs what the ring saves; at B = 128 the ring with split-K: 63 us)
   const bool deep_k = p.M <= 16384 && d.Kpad >= 4096 && tiles128 < 512;
   if (deep > 0 && bf && p.fast && d.to == d.ti && d.N >= 256 && d.Kpad >= 1024 && d.N % 128 == 0 &&
       ((p.M <= 8192 && tiles128 < 256) || deep_k)) {
-    p.BM = 128; p.BN = 128; p.BK = 32; p.stages = deep;
+    p.BM = 128; p.BN = 128; p.BK = 32; p.deep = true;
   }
 #ifdef GHOST_TUNING
   static const char* force_tile = getenv("GHOST_CONV_TILE");   // tuning knob "BMxBN"
@@ -795,7 +842,7 @@ Plan make_plan(const ConvDesc& d) {
   int s = 1;
   if (d.force_split > 0) {
     s = d.force_split;
-  } else if (p.stages > 0) {
+  } else if (p.deep) {
     // deep ring: one resident workgroup per CU; split K until the grid covers the CUs
     // (GHOST_SPLIT_DEEP: the grid target in workgroups, tuning build)
     static const int deep_target = GHOST_KNOB("GHOST_SPLIT_DEEP", 256);
@@ -818,13 +865,111 @@ Plan make_plan(const ConvDesc& d) {
   if (s > nk) s = nk;
   p.kt_per_split = (nk + s - 1) / s;
   p.nsplit = (nk + p.kt_per_split - 1) / p.kt_per_split;
-  // bf16 operands with an fp32 output (the ArcFace embedding layer): the GEMM always writes fp32
+  // 16-bit operands with an fp32 output (the ArcFace embedding layer): the GEMM always writes fp32
   // partials and the reduction kernel applies the epilogue in fp32
-  p.partial = p.nsplit > 1 || (is16(d.ti) && d.to == GHOST_F32);
+  const bool f32_from16 = bf && d.to == GHOST_F32;
+  p.partial = p.nsplit > 1 || f32_from16;
+  if (p.partial) p.ws_bytes = (size_t)p.npar * p.nsplit * p.M * p.NT * sizeof(float);
+  p.grid[0] = (unsigned)(p.nMt * p.nNt); p.grid[1] = (unsigned)p.nsplit; p.grid[2] = (unsigned)p.npar;
+
+  // ---- what cannot run: weight rows / K the packing does not hold, a type pair without kernels ----
+  if (p.NT > d.Npad) return p;   // weight rows read by the last tile must exist
+  if (d.Kpad < (d.kind == CONV_T4S2 ? 4 * d.Cin : d.kh * d.kw * d.Cin)) return p;
+  if (f32_from16 ? (d.ti != GHOST_BF16 || d.res || d.y2 || d.epi != EPI_STD) : (bf ? d.to != d.ti : !(d.to == GHOST_F32 || is16(d.to))))
+    return p;
+
+  // ---- the kernel: the ring where it has an instance, else the register-staged tile ----
+  // (the partial-sum GEMM under an fp32 output does not depend on the output type: the 16-bit instances)
+  p.to = f32_from16 ? d.ti : d.to;
+  IgemmKernel kernel = IgemmKernel::None;
+  static const int use_v2 = GHOST_KNOB("GHOST_CONV_V2", 1);
+  // measured (tools/bench_ops.py): the DMA ring wins on the 128-row tiles, loses on 256x64
+  static const int aad_glds = GHOST_KNOB("GHOST_CONV_AAD_GLDS", 0);   // AAD epilogue on the 3-stage ring
+  static const int stages_knob = GHOST_KNOB("GHOST_CONV_STAGES", 3);   // the ring's stages outside the deep plans
+  if (use_v2 && bf && !f32_from16 && p.fast && p.BK == 32 && (d.epi != EPI_AAD || p.deep || aad_glds) && p.BM <= 128) {
+    // warp-specialised DMA waves (B = 64, same box: 4x4 3x3 1024 conv 50 -> 41 us, encoder conv5..7 49 / 47 / 32 ->
+    // 40 / 38 / 28, deconv2 82 -> 64; bench +0.4..1.8 %)
+    static const int ws = GHOST_KNOB("GHOST_CONV_WS", 1);
+    p.stages = p.deep ? deep : stages_knob;
+    p.wsl = ws ? 4 : 0;
+    p.kepi = p.nsplit > 1 ? KEPI_SPLIT : d.epi == EPI_AAD ? KEPI_AAD : KEPI_STD;
+    p.fn = glds_fn(d.ti, p.BM, p.BN, p.stages, p.kepi, p.wsl);
+    if (p.fn) kernel = IgemmKernel::Glds;
+  }
+  if (kernel == IgemmKernel::None) {
+    p.stages = p.wsl = 0;
+    p.kepi = p.partial ? KEPI_SPLIT : d.epi == EPI_AAD ? KEPI_AAD : KEPI_STD;
+    p.fn = igemm_fn(d.ti, p.to, p.BM, p.BN, p.BK, p.kepi, p.fast);
+    if (!p.fn) return p;
+    kernel = IgemmKernel::Igemm;
+  }
+  p.block = p.wsl ? 512 : 256;
+
+  // ---- split-K fix-up in the GEMM (split_fixup) when the caller gave counters and a tile's partials are small
+  // enough for one workgroup to sum them (the last one to finish does it while the rest of the grid has drained):
+  // B = 1 and the generator's 2x2..8x8 stages; the large splits keep splitk_reduce_kernel over the whole chip
+  // (16-bit operands with an fp32 output keep it too: their reduction writes another type than the GEMM's)
+  // (the last arriver reads ~1 us per 16 KB of partials, cdna_hip_programming.md §6 item 2: a few tens of KB per
+  // tile; they are staged in the kernel's LDS, so never more than that holds.  Measured at B = 1 bf16: 32-40 KB
+  // 1.10-1.11 ms as without the fix-up, 128 KB — the deep ring's 4x4 / 8x8 GEMMs fused — 1.17-1.19 ms)
+  static const int fuse_knob = GHOST_KNOB("GHOST_SPLIT_FUSE", 1);
+  static const long fuse_max = (long)GHOST_KNOB("GHOST_SPLIT_FUSE_KB", 32) << 10;
+  if (p.nsplit > 1 && d.sem && fuse_knob && !f32_from16 && (long)tiles <= d.nsem) {
+    const long tile_bytes = (long)p.nsplit * (p.M < p.BM ? p.M : p.BM) * p.BN * 4;
+    // LDS of the kernel that runs it: the deep ring has stages x 16 KB; otherwise the smaller of the 3-stage ring
+    // and conv_igemm_kernel's buffers
+    const long ring = (long)(p.deep ? deep : stages_knob) * (p.BM + p.BN) * 64;
+    const long bufs = 2L * (p.BM + p.BN) * (p.BK + vec) * esz;
+    // (the min dates from when this bound was taken before the kernel was known; dropping it is a retune)
+    const long lds = p.deep && kernel == IgemmKernel::Glds ? ring : (ring < bufs ? ring : bufs);
+    if (tile_bytes <= lds && (fuse_knob == 2 || tile_bytes <= fuse_max)) p.fixup = d.epi == EPI_AAD ? 2 : 1;
+  }
+
+  // ---- the reduction that follows a GEMM of partials without the fix-up ----
+  if (p.partial && !p.fixup) {
+    const int ncols = d.epi == EPI_AAD ? d.C_aad : d.N;
+    static const int vec4 = GHOST_KNOB("GHOST_SPLITK_VEC", 1);   // four channels per thread when the columns allow it
+    p.reduce = f32_from16 ? IgemmReduce::F32From16
+               : vec4 && ncols % 4 == 0 && p.NT % 4 == 0 ? IgemmReduce::Reduce4 : IgemmReduce::Reduce;
+    const long total = (long)p.M * ncols;
+    p.reduce_grid = (unsigned)(((p.reduce == IgemmReduce::Reduce4 ? total / 4 : total) + 255) / 256);
+    p.reduce_fn = reduce_fn(d.to, d.epi == EPI_AAD ? KEPI_AAD : KEPI_STD, p.reduce == IgemmReduce::Reduce4);
+  }
+  p.kernel = kernel;
   return p;
 }
 
-ConvArgs make_args(const ConvDesc& d, const Plan& p, float* partial) {
+// the GEMM's line: the kernel with its template parameters and the edge classes of the launch (plan_log.h), for a
+// kernel whose ring prologue holds stages - 1 K steps (the register-staged kernel: 2).  No M, no split count: only
+// the classes they fall in.
+PlanSig igemm_signature(const IgemmPlan& p, const ConvDesc& d) {
+  const bool glds = p.kernel == IgemmKernel::Glds;
+  const int bk = glds ? 32 : p.BK, st = glds ? p.stages : 2;
+  const int nk = d.Kpad / bk, last = nk % p.kt_per_split;
+  PlanSig g;
+  int n = glds ? snprintf(g.s, sizeof(g.s), "glds t=%s %dx%d stages=%d ws=%d", plan_dt(d.ti), p.BM, p.BN, p.stages, p.wsl)
+               : snprintf(g.s, sizeof(g.s), "igemm ti=%s to=%s %dx%dx%d fast=%d", plan_dt(d.ti), plan_dt(p.to), p.BM, p.BN,
+                          p.BK, (int)p.fast);
+  snprintf(g.s + n, sizeof(g.s) - n, " epi=%s kind=%s split=%d ragged=%d short=%d lastshort=%d fixup=%s mtail=%d ntail=%d%s",
+           kepi_name(p.kepi), d.kind == CONV_T4S2 ? "T4S2" : "FWD", p.nsplit > 1, last != 0, p.kt_per_split < st - 1,
+           last != 0 && last < st - 1, !p.fixup ? "none" : p.fixup == 2 ? "aad" : "std", p.M % p.BM != 0,
+           d.N % p.BN != 0, p.fixup ? (p.M < p.BM ? " fixrows=M" : " fixrows=BM") : "");
+  return g;
+}
+
+PlanSig igemm_reduce_signature(const IgemmPlan& p, const ConvDesc& d) {
+  PlanSig g;
+  if (p.reduce == IgemmReduce::F32From16)
+    snprintf(g.s, sizeof(g.s), "splitk_reduce to=f32 epi=STD from=%s", plan_dt(d.ti));
+  else
+    snprintf(g.s, sizeof(g.s), "splitk_reduce%s to=%s epi=%s", p.reduce == IgemmReduce::Reduce4 ? "4" : "", plan_dt(d.to),
+             kepi_name(d.epi == EPI_AAD ? KEPI_AAD : KEPI_STD));
+  return g;
+}
+
+namespace {
+
+ConvArgs make_args(const ConvDesc& d, const IgemmPlan& p, float* partial) {
   ConvArgs a{};
   a.x = d.x; a.w = d.w; a.y = d.y;
   a.scale = d.scale; a.shift = d.shift; a.res = d.res;
@@ -845,236 +990,63 @@ ConvArgs make_args(const ConvDesc& d, const Plan& p, float* partial) {
   }
   a.nsplit = p.nsplit; a.kt_per_split = p.kt_per_split;
   a.slope = d.slope; a.tanh_out = d.tanh_out;
-  a.nmajor = p.stages > 0 ? GHOST_KNOB("GHOST_CONV_NMAJOR", 1) : 0;
+  a.nmajor = p.deep ? GHOST_KNOB("GHOST_CONV_NMAJOR", 1) : 0;
+  if (p.fixup) { a.sem = d.sem; a.fuse = p.fixup; }
   return a;
 }
 
-// plan log: the edge classes of a GEMM launch (plan_log.h), for a kernel whose ring prologue holds `stages` - 1
-// K steps (the register-staged kernel: 2).  No M, no split count: only the classes they fall in.
-struct PlanEdges { char s[128]; };
-PlanEdges plan_edges(const ConvArgs& a, const Plan& p, int bk, int stages) {
-  PlanEdges e;
-  const int nk = a.Kpad / bk, last = nk % a.kt_per_split;
-  snprintf(e.s, sizeof(e.s), "split=%d ragged=%d short=%d lastshort=%d fixup=%s mtail=%d ntail=%d%s", a.nsplit > 1,
-           last != 0, a.kt_per_split < stages - 1, last != 0 && last < stages - 1,
-           !a.sem ? "none" : a.fuse == 2 ? "aad" : "std", a.M % p.BM != 0, a.N % p.BN != 0,
-           a.sem ? (a.M < p.BM ? " fixrows=M" : " fixrows=BM") : "");
-  return e;
-}
-
-template <typename TI, typename TO, int BM, int BN, int BK, int EPI, bool FAST>
-void launch_gemm(const ConvArgs& a, const Plan& p, hipStream_t s) {
-  dim3 grid(p.nMt * p.nNt, p.nsplit, p.npar);
-  GHOST_PLAN_LOG("igemm ti=%s to=%s %dx%dx%d fast=%d epi=%s kind=%s %s", plan_dt(gdt<TI>()), plan_dt(gdt<TO>()), BM, BN,
-                 BK, (int)FAST, kepi_name(EPI), a.deconv ? "T4S2" : "FWD", plan_edges(a, p, BK, 2).s);
-  hipLaunchKernelGGL((conv_igemm_kernel<TI, TO, BM, BN, BK, EPI, FAST>), grid, dim3(256), 0, s, a);
-}
-
-// instantiated configurations (BM x BN x BK); anything else is rejected by the plan
-template <typename TI, typename TO, int EPI, bool FAST>
-int dispatch_tile(const ConvArgs& a, const Plan& p, hipStream_t s) {
-  const int key = p.BM * 100000 + p.BN * 100 + p.BK;
-#define GHOST_TILE(bm, bn, bk) \
-  case bm * 100000 + bn * 100 + bk: launch_gemm<TI, TO, bm, bn, bk, EPI, FAST>(a, p, s); return 0;
-  if constexpr (!FAST) {
-    if constexpr (EPI != KEPI_AAD) {
-      switch (key) { GHOST_TILE(256, 32, 32) GHOST_TILE(64, 64, 32) default: break; }
-    }
-    return -1;
-  } else if constexpr (sizeof(TI) == 2) {
-    if constexpr (EPI == KEPI_AAD) {
-      switch (key) { GHOST_TILE(128, 128, 32) GHOST_TILE(128, 128, 64) GHOST_TILE(64, 128, 32)
-                     GHOST_TILE(64, 128, 64) default: break; }
-    } else {
-      switch (key) { GHOST_TILE(128, 128, 32) GHOST_TILE(128, 128, 64) GHOST_TILE(64, 128, 32)
-                     GHOST_TILE(64, 128, 64) GHOST_TILE(256, 64, 32) GHOST_TILE(256, 64, 64)
-                     GHOST_TILE(256, 32, 32) GHOST_TILE(256, 32, 64) GHOST_TILE(256, 16, 32)
-                     GHOST_TILE(256, 16, 64) GHOST_TILE(128, 64, 32) GHOST_TILE(128, 64, 64)
-                     GHOST_TILE(64, 64, 32) GHOST_TILE(64, 64, 64) GHOST_TILE(128, 32, 32)
-                     GHOST_TILE(128, 16, 32) default: break; }
-    }
-    return -1;
-  } else {
-    if constexpr (EPI == KEPI_AAD) {
-      switch (key) { GHOST_TILE(128, 128, 32) GHOST_TILE(64, 128, 32) default: break; }
-    } else {
-      switch (key) { GHOST_TILE(128, 128, 32) GHOST_TILE(64, 128, 32) GHOST_TILE(256, 64, 32)
-                     GHOST_TILE(256, 32, 32) GHOST_TILE(256, 16, 32) default: break; }
-    }
-    return -1;
+int conv_igemm(const ConvDesc& d, void* ws, size_t ws_bytes, hipStream_t s) {
+  const IgemmPlan p = igemm_plan(d);
+  if (p.kernel == IgemmKernel::None) return -1;
+  if (p.partial && (!ws || ws_bytes < p.ws_bytes)) return -1;
+  const ConvArgs a = make_args(d, p, p.partial ? reinterpret_cast<float*>(ws) : nullptr);
+  GHOST_PLAN_LOG("%s", igemm_signature(p, d).s);
+  hipLaunchKernelGGL(p.fn, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(p.block), 0, s, a);
+  if (p.reduce != IgemmReduce::None) {
+    GHOST_PLAN_LOG("%s", igemm_reduce_signature(p, d).s);
+    hipLaunchKernelGGL(p.reduce_fn, dim3(p.reduce_grid, 1, p.npar), dim3(256), 0, s, a);
   }
-#undef GHOST_TILE
-}
-
-template <typename T, int EPI>
-bool launch_glds(const ConvArgs& a, const Plan& p, hipStream_t s) {
-  static const int stages_knob = GHOST_KNOB("GHOST_CONV_STAGES", 3);
-  // warp-specialised DMA waves (B = 64, same box: 4x4 3x3 1024 conv 50 -> 41 us, encoder conv5..7 49 / 47 / 32 ->
-  // 40 / 38 / 28, deconv2 82 -> 64; bench +0.4..1.8 %)
-  static const int ws = GHOST_KNOB("GHOST_CONV_WS", 1);
-  const int stages = p.stages > 0 ? p.stages : stages_knob;
-  dim3 grid(p.nMt * p.nNt, p.nsplit, p.npar);
-#define GHOST_G_LOG(bm, bn, st, wsl)                                                                       \
-  GHOST_PLAN_LOG("glds t=%s %dx%d stages=%d ws=%d epi=%s kind=%s %s", plan_dt(gdt<T>()), bm, bn, st, wsl,    \
-                 kepi_name(EPI), a.deconv ? "T4S2" : "FWD", plan_edges(a, p, 32, st).s)
-  if constexpr (EPI == KEPI_AAD) {
-    if (p.BM == 128 && p.BN == 128 && stages == 8) {
-      GHOST_G_LOG(128, 128, 8, ws ? 4 : 0);
-      if (ws)
-        hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, 8, EPI, 4>), grid, dim3(512), 0, s, a);
-      else
-        hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, 8, EPI>), grid, dim3(256), 0, s, a);
-      return true;
-    }
-    if (p.BM == 128 && p.BN == 128 && stages == 3 && ws) {
-      GHOST_G_LOG(128, 128, 3, 4);
-      hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, 3, EPI, 4>), grid, dim3(512), 0, s, a);
-      return true;
-    }
-    return false;
-  }
-#define GHOST_G(bm, bn, st)                                                                      \
-  if (p.BM == bm && p.BN == bn && stages == st) {                                                \
-    GHOST_G_LOG(bm, bn, st, ws ? 4 : 0);                                                          \
-    if (ws)                                                                                       \
-      hipLaunchKernelGGL((conv_glds_kernel<T, bm, bn, st, EPI, 4>), grid, dim3(512), 0, s, a);      \
-    else                                                                                          \
-      hipLaunchKernelGGL((conv_glds_kernel<T, bm, bn, st, EPI>), grid, dim3(256), 0, s, a);         \
-    return true;                                                                                  \
-  }
-  GHOST_G(128, 128, 8) GHOST_G(128, 128, 6)
-  GHOST_G(128, 128, 4) GHOST_G(256, 64, 4) GHOST_G(128, 64, 4) GHOST_G(64, 128, 4)
-  GHOST_G(128, 128, 3) GHOST_G(256, 64, 3) GHOST_G(128, 64, 3) GHOST_G(64, 128, 3)
-#undef GHOST_G
-#undef GHOST_G_LOG
-  return false;
-}
-
-template <typename TI, typename TO>
-int dispatch_types(const ConvDesc& d, const ConvArgs& a, const Plan& p, hipStream_t s) {
-  int rc;
-  if constexpr (sizeof(TI) == 2 && sizeof(TO) == 4) {
-    // bf16 GEMM, fp32 epilogue: the partial-sum GEMM does not depend on the output type, so it
-    // shares the bf16 instantiations; the reduction writes fp32
-    if (!p.partial || d.epi != EPI_STD) return -1;
-    rc = p.fast ? dispatch_tile<TI, TI, KEPI_SPLIT, true>(a, p, s) : dispatch_tile<TI, TI, KEPI_SPLIT, false>(a, p, s);
-    if (rc) return rc;
-    const long total = (long)p.M * d.N;
-    dim3 grid((unsigned)((total + 255) / 256), 1, p.npar);
-    GHOST_PLAN_LOG("splitk_reduce to=f32 epi=STD from=%s", plan_dt(gdt<TI>()));
-    hipLaunchKernelGGL((splitk_reduce_kernel<float, KEPI_STD>), grid, dim3(256), 0, s, a);
-    return 0;
-  } else {
-  static const int use_v2 = GHOST_KNOB("GHOST_CONV_V2", 1);
-  if constexpr (sizeof(TI) == 2 && sizeof(TO) == 2) {
-    // measured (tools/bench_ops.py): the DMA ring wins on the 128-row tiles, loses on 256x64
-    static const int aad_glds = GHOST_KNOB("GHOST_CONV_AAD_GLDS", 0);   // AAD epilogue on the 3-stage ring
-    if (use_v2 && p.fast && p.BK == 32 && (d.epi != EPI_AAD || p.stages > 0 || aad_glds) && p.BM <= 128 &&
-        p.partial == (p.nsplit > 1)) {
-      const bool ok = p.nsplit > 1 ? launch_glds<TI, KEPI_SPLIT>(a, p, s)
-                                   : (d.epi == EPI_AAD ? launch_glds<TI, KEPI_AAD>(a, p, s) : launch_glds<TI, KEPI_STD>(a, p, s));
-      if (ok) {
-        if (p.nsplit > 1 && !a.sem) {
-          if (d.epi == EPI_AAD) launch_reduce<TO, KEPI_AAD>(a, d.C_aad, p.npar, s);
-          else launch_reduce<TO, KEPI_STD>(a, d.N, p.npar, s);
-        }
-        return 0;
-      }
-    }
-  }
-  if (p.partial) {
-    rc = p.fast ? dispatch_tile<TI, TO, KEPI_SPLIT, true>(a, p, s) : dispatch_tile<TI, TO, KEPI_SPLIT, false>(a, p, s);
-    if (rc || a.sem) return rc;
-    if (d.epi == EPI_AAD) launch_reduce<TO, KEPI_AAD>(a, d.C_aad, p.npar, s);
-    else launch_reduce<TO, KEPI_STD>(a, d.N, p.npar, s);
-    return 0;
-  }
-  if (d.epi == EPI_AAD) {
-    if (!p.fast) return -1;
-    return dispatch_tile<TI, TO, KEPI_AAD, true>(a, p, s);
-  }
-  return p.fast ? dispatch_tile<TI, TO, KEPI_STD, true>(a, p, s) : dispatch_tile<TI, TO, KEPI_STD, false>(a, p, s);
-  }
+  return (int)hipGetLastError();
 }
 
 }  // namespace
 
+bool conv_desc_ok(const ConvDesc& d) {
+  if (!d.x || !d.w || !d.y || d.B <= 0 || d.Cin <= 0 || d.N <= 0) return false;
+  if (d.Kpad % 32 != 0 || d.Npad < d.N) return false;
+  if (d.y2 && (!d.scale2 || !d.shift2 || d.epi != EPI_STD)) return false;
+  if (d.kind == CONV_FWD && (d.kh * d.kw > 64 || d.kh < 1 || d.kw < 1 || d.stride < 1)) return false;   // 64-bit tap masks
+  return d.epi != EPI_AAD ||
+         (d.C_aad % 16 == 0 && d.N == 2 * d.C_aad && d.hin && d.stat && d.idgb && d.mask && d.shift);
+}
+
 size_t conv_workspace_bytes(const ConvDesc& d) {
-  if (conv3x3_halo_supported(d) || convT_halo_supported(d) || conv_stem3x3_supported(d) ||
-      conv4x4s2_patch_supported(d))
-    return 0;
-  if (conv_first_supported(d)) return conv_first_workspace_bytes();
-  Plan p = make_plan(d);
-  if (!p.partial) return 0;
-  return (size_t)p.npar * p.nsplit * p.M * p.NT * sizeof(float);
+  switch (conv_path(d)) {
+    case ConvPath::First: return conv_first_workspace_bytes();
+    case ConvPath::Igemm: return igemm_plan(d).ws_bytes;
+    default: return 0;
+  }
 }
 
 int conv_launch(const ConvDesc& d, void* ws, size_t ws_bytes, hipStream_t stream) {
-  if (!d.x || !d.w || !d.y || d.B <= 0 || d.Cin <= 0 || d.N <= 0) return -1;
-  if (d.Kpad % 32 != 0 || d.Npad < d.N) return -1;
-  if (d.y2 && (!d.scale2 || !d.shift2 || d.epi != EPI_STD)) return -1;
-  if (d.kind == CONV_FWD && (d.kh * d.kw > 64 || d.kh < 1 || d.kw < 1 || d.stride < 1)) return -1;   // 64-bit tap masks
-  if (d.epi == EPI_AAD && (d.C_aad % 16 != 0 || d.N != 2 * d.C_aad || !d.hin || !d.stat || !d.idgb || !d.mask || !d.shift))
-    return -1;
+  if (!conv_desc_ok(d)) return -1;
+  const ConvPath path = conv_path(d);
 #ifdef GHOST_TUNING
   // plan listing for profiling (tuning builds only): one line per conv launch with its shape
   static const int trace = GHOST_KNOB("GHOST_CONV_TRACE", 0);
   if (trace)
     fprintf(stderr, "[conv] kind=%d B=%d %dx%d Cin=%d N=%d k=%dx%d s=%d halo=%d\n", (int)d.kind, d.B, d.Hi, d.Wi, d.Cin,
-            d.N, d.kh, d.kw, d.stride, (int)conv3x3_halo_supported(d));
+            d.N, d.kh, d.kw, d.stride, (int)(path == ConvPath::Halo3x3));
 #endif
-  if (conv3x3_halo_supported(d)) return conv3x3_halo(d, stream);
-  if (conv_first_supported(d)) return conv_first(d, ws, ws_bytes, stream);
-  if (conv_stem3x3_supported(d)) return conv_stem3x3(d, stream);
-  if (convT_halo_supported(d)) return convT_halo(d, stream);
-  if (conv4x4s2_patch_supported(d) || conv3x3s2_patch_supported(d)) return conv_s2_patch(d, stream);
-  Plan p = make_plan(d);
-  if (p.NT > d.Npad) return -1;  // weight rows read by the last tile must exist
-  const int K = d.kind == CONV_T4S2 ? 4 * d.Cin : d.kh * d.kw * d.Cin;
-  if (d.Kpad < K) return -1;
-  float* partial = nullptr;
-  if (p.partial) {
-    size_t need = (size_t)p.npar * p.nsplit * p.M * p.NT * sizeof(float);
-    if (!ws || ws_bytes < need) return -1;
-    partial = reinterpret_cast<float*>(ws);
+  switch (path) {
+    case ConvPath::Halo3x3: return conv3x3_halo(d, stream);
+    case ConvPath::First: return conv_first(d, ws, ws_bytes, stream);
+    case ConvPath::Stem3x3: return conv_stem3x3(d, stream);
+    case ConvPath::ConvTHalo: return convT_halo(d, stream);
+    case ConvPath::S2Patch: return conv_s2_patch(d, stream);
+    case ConvPath::Igemm: break;
   }
-  ConvArgs a = make_args(d, p, partial);
-  // split-K fix-up in the GEMM (split_fixup) when the caller gave counters and a tile's partials are small enough
-  // for one workgroup to sum them (the last one to finish does it while the rest of the grid has drained):
-  // B = 1 and the generator's 2x2..8x8 stages; the large splits keep splitk_reduce_kernel over the whole chip
-  // (bf16 operands with an fp32 output keep it too: their reduction writes another type than the GEMM's)
-  // (the last arriver reads ~1 us per 16 KB of partials, cdna_hip_programming.md §6 item 2: a few tens of KB per
-  // tile; they are staged in the kernel's LDS, so never more than that holds.  Measured at B = 1 bf16: 32-40 KB
-  // 1.10-1.11 ms as without the fix-up, 128 KB — the deep ring's 4x4 / 8x8 GEMMs fused — 1.17-1.19 ms)
-  static const int fuse_knob = GHOST_KNOB("GHOST_SPLIT_FUSE", 1);
-  static const long fuse_max = (long)GHOST_KNOB("GHOST_SPLIT_FUSE_KB", 32) << 10;
-  if (p.partial && p.nsplit > 1 && d.sem && fuse_knob && !(is16(d.ti) && d.to == GHOST_F32) &&
-      (long)p.nMt * p.nNt * p.npar <= d.nsem) {
-    const long tile_bytes = (long)p.nsplit * (p.M < p.BM ? p.M : p.BM) * p.BN * 4;
-    // LDS of the kernel that runs it: the deep ring (p.stages, always conv_glds_kernel: 16-bit, fast, 128 x 128)
-    // has stages x 16 KB; otherwise the smaller of conv_glds_kernel's 3-stage ring and conv_igemm_kernel's buffers
-    const int vec = is16(d.ti) ? 8 : 4, esz = is16(d.ti) ? 2 : 4;
-    static const int stages_knob = GHOST_KNOB("GHOST_CONV_STAGES", 3);
-    const long ring = (long)(p.stages > 0 ? p.stages : stages_knob) * (p.BM + p.BN) * 64;
-    const long bufs = 2L * (p.BM + p.BN) * (p.BK + vec) * esz;
-    static const int use_v2 = GHOST_KNOB("GHOST_CONV_V2", 1);
-    const bool deep_glds = use_v2 && (p.stages == 8 || p.stages == 6 || p.stages == 4);   // launch_glds' instances
-    const long lds = deep_glds ? ring : (ring < bufs ? ring : bufs);
-    if (tile_bytes <= lds && (fuse_knob == 2 || tile_bytes <= fuse_max)) {
-      a.sem = d.sem;
-      a.fuse = d.epi == EPI_AAD ? 2 : 1;
-    }
-  }
-  int rc;
-  if (d.ti == GHOST_F32 && d.to == GHOST_F32) rc = dispatch_types<float, float>(d, a, p, stream);
-  else if (d.ti == GHOST_BF16 && d.to == GHOST_BF16) rc = dispatch_types<bf16, bf16>(d, a, p, stream);
-  else if (d.ti == GHOST_F32 && d.to == GHOST_BF16) rc = dispatch_types<float, bf16>(d, a, p, stream);
-  else if (d.ti == GHOST_F16 && d.to == GHOST_F16) rc = dispatch_types<_Float16, _Float16>(d, a, p, stream);
-  else if (d.ti == GHOST_F32 && d.to == GHOST_F16) rc = dispatch_types<float, _Float16>(d, a, p, stream);
-  else if (d.ti == GHOST_BF16 && d.to == GHOST_F32 && !d.res && !d.y2) rc = dispatch_types<bf16, float>(d, a, p, stream);
-  else return -1;
-  if (rc) return rc;
-  return (int)hipGetLastError();
+  return conv_igemm(d, ws, ws_bytes, stream);
 }
 
 }  // namespace ghost

@@ -12,6 +12,7 @@ bool conv4x4s2_patch_supported(const ConvDesc& d);
 // IResNet's 3x3/s2/p1 convs (IBasicBlock epilogue: BN, PReLU, residual, second output)
 bool conv3x3s2_patch_supported(const ConvDesc& d);
 // either form (d.kh = 4 or 3)
+PlanSig conv_s2_patch_signature(const ConvDesc& d);
 int conv_s2_patch(const ConvDesc& d, hipStream_t s);
 
 }  // namespace ghost

@@ -252,6 +252,13 @@ bool conv3x3s2_patch_supported(const ConvDesc& d) {
   return (long)d.Hi * d.Wi * d.ldx < (1L << 31) && (long)d.B * Ho * Wo * d.ldy < (1L << 31);
 }
 
+PlanSig conv_s2_patch_signature(const ConvDesc& d) {
+  PlanSig g;
+  snprintf(g.s, sizeof(g.s), "s2_patch t=%s K=%d ncb=%d N=%d overhang=%d", plan_dt(d.ti), d.kh, d.Cin / 32, d.N,
+           (d.Hi / 2) % TH != 0 || (d.Wi / 2) % TW != 0);
+  return g;
+}
+
 int conv_s2_patch(const ConvDesc& d, hipStream_t s) {
   const int K = d.kh;
   if (K == 4 ? !conv4x4s2_patch_supported(d) : !conv3x3s2_patch_supported(d)) return -1;
@@ -267,8 +274,7 @@ int conv_s2_patch(const ConvDesc& d, hipStream_t s) {
   a.y2 = d.y2; a.ldy2 = d.ldy2; a.scale2 = d.scale2; a.shift2 = d.shift2;
   dim3 grid((unsigned)(d.B * a.tiles_per_img), (unsigned)(d.N / BN));
   const bool h16 = d.ti == GHOST_F16;
-  GHOST_PLAN_LOG("s2_patch t=%s K=%d ncb=%d N=%d overhang=%d", plan_dt(d.ti), K, a.ncb, d.N,
-                 a.Ho % TH != 0 || a.Wo % TW != 0);
+  GHOST_PLAN_LOG("%s", conv_s2_patch_signature(d).s);
   if (K == 4) {
     if (h16) hipLaunchKernelGGL((conv_s2_patch_kernel<_Float16, 4>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((conv_s2_patch_kernel<bf16, 4>), grid, dim3(256), 0, s, a);

@@ -449,6 +449,23 @@ int64_t ghost_plan_log_read(char* buf, int64_t cap);
  * neither aad_v3 nor aad_wide takes the shape (the fused kernel or the mask pass + GEMM epilogue would). */
 int64_t ghost_aad_plan(int dtype, int B, int H, int W, int C, int Ca, int L, int up2x, int zp_mask, float slope,
                        int lda, int ldh, const int ldo[], char* buf, int64_t cap);
+/* Test support, touches no device: the newline-separated signatures, in launch order, that one convolution launch
+ * of this descriptor would append to the plan log (the kernel's line, then a split-K reduction's), from the same
+ * family rule, planners and formatters as the launch.  ti / to: GhostDType of operands and output; kind 0: Conv2d
+ * kh x kw / stride / pad, 1: ConvTranspose2d 4x4/s2/p1; epi 0: standard, 1: the AADLayer epilogue (N = 2 C);
+ * split_k > 0 forces the split; min_wgs as the runtime's small-batch hint (0: none); nsem: arrival counters offered
+ * to the split-K fix-up (0: none; the runtime gives 4096); ncu: the device's compute units (MI355X: 256); flags: which
+ * optional pointers the descriptor sets.  Every pointer counts as 16-byte aligned, ldres = ldy2 = ldy.  *ws_bytes
+ * (may be NULL) receives the workspace the launch needs.  Copies the NUL-terminated text into buf (at most cap bytes;
+ * buf = NULL with cap = 0 asks for the size) and returns the bytes needed including the NUL, or GHOST_EINVAL when
+ * the launch would be refused. */
+enum {
+  GHOST_CONV_PLAN_RES = 1, GHOST_CONV_PLAN_RES_FIRST = 2, GHOST_CONV_PLAN_PRELU = 4, GHOST_CONV_PLAN_Y2 = 8,
+  GHOST_CONV_PLAN_U8 = 16, GHOST_CONV_PLAN_TANH = 32, GHOST_CONV_PLAN_IN_PART = 64, GHOST_CONV_PLAN_FLAGS = 127
+};
+int64_t ghost_conv_plan(int ti, int to, int kind, int B, int H, int W, int Cin, int ldx, int N, int Npad, int Kpad,
+                        int kh, int kw, int stride, int pad, int ldy, int epi, int split_k, int min_wgs, int nsem,
+                        int ncu, int flags, int64_t* ws_bytes, char* buf, int64_t cap);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases
 from oracle import aei_ref, golden_io
 
 pytestmark = pytest.mark.gpu
@@ -367,8 +368,8 @@ def test_conv3x3_splitk_residual_tanh(lib, split):
 # forms, the non-FAST gather with 16-bit operands.  Every case: bf16 and fp16, against a float64 conv of the
 # storage-rounded operands within 1.01 ulp of the storage type (test_conv3x3_64_op's gate), the output pre-filled
 # with NaN, ldy > Cout with a sentinel that must survive, and the plan log (ghost_plan_log) must show the intended
-# class.  The shapes were derived by hand from conv_igemm.hip make_plan; split_k > 0 keeps a conv off the halo and
-# patch kernels.  If a retuned heuristic moves a case to another variant, change the shape, not the class.
+# class.  The cases live in tests/conv_cases.py; tests/test_conv_plan_cpu.py checks on a machine with no GPU that the
+# planner (igemm_plan, through ghost_conv_plan) gives every one of them its tokens.
 # ----------------------------------------------------------------------------------------
 SENTINEL = 7.0
 
@@ -398,43 +399,8 @@ def _ulp_gate(got, ref, dt):
     assert float((d / ref.abs().clamp_min(1.0)).max()) <= 1.01 * ulp, float(d.max())
 
 
-IGEMM_EDGES = [
-    # cin, ldx, cout, k, s, p, B, H, W, split_k, plan tokens (GEMM launch), reduction kernel
-    # glds 64x128, 3 stages, M = 120 (tail), non-square; nk = 27: splits 7,7,7,6 / one K step each / clamped to nk
-    (96, 96, 128, 3, 1, 1, 2, 6, 10, 4, ("glds", "64x128", "stages=3", "split=1", "ragged=1", "short=0", "mtail=1"),
-     "splitk_reduce4"),
-    (96, 96, 128, 3, 1, 1, 2, 6, 10, 27, ("glds", "64x128", "stages=3", "split=1", "ragged=0", "short=1", "mtail=1"),
-     "splitk_reduce4"),
-    (96, 96, 128, 3, 1, 1, 2, 6, 10, 100, ("glds", "64x128", "stages=3", "split=1", "ragged=0", "short=1", "mtail=1"),
-     "splitk_reduce4"),
-    # N tail: Cout 200 reduces four channels at a time, Cout 130 one
-    (64, 64, 200, 3, 1, 1, 3, 5, 7, 2, ("glds", "64x128", "split=1", "ntail=1", "mtail=1"), "splitk_reduce4"),
-    (64, 64, 130, 3, 1, 1, 3, 5, 7, 2, ("glds", "64x128", "split=1", "ntail=1", "mtail=1"), "splitk_reduce"),
-    # deep ring 128x128 x 8 stages; nk = 36: splits 8,8,8,8,4 (the last shorter than STAGES - 1) / one K step each
-    (128, 128, 256, 3, 1, 1, 2, 8, 8, 5, ("glds", "128x128", "stages=8", "split=1", "ragged=1", "lastshort=1",
-                                          "mtail=0"), "splitk_reduce4"),
-    (128, 128, 256, 3, 1, 1, 3, 5, 7, 5, ("glds", "128x128", "stages=8", "split=1", "ragged=1", "lastshort=1",
-                                          "mtail=1"), "splitk_reduce4"),
-    (128, 128, 256, 3, 1, 1, 2, 8, 8, 36, ("glds", "128x128", "stages=8", "split=1", "short=1", "mtail=0"),
-     "splitk_reduce4"),
-    (128, 128, 256, 3, 1, 1, 3, 5, 7, 36, ("glds", "128x128", "stages=8", "split=1", "short=1", "mtail=1"),
-     "splitk_reduce4"),
-    # the encoder's 4x4/s2 tile on the ring
-    (32, 32, 64, 4, 2, 1, 1, 12, 20, 2, ("glds", "128x64", "split=1", "mtail=1"), "splitk_reduce4"),
-    # register-staged kernel, 256x32 tile, 16-bit split
-    (64, 64, 24, 3, 1, 1, 2, 9, 5, 3, ("igemm", "256x32x32", "fast=1", "epi=SPLIT", "split=1", "ntail=1", "mtail=1"),
-     "splitk_reduce4"),
-    # 1x1/s2 (nk = 5): unsplit and one K step per split
-    (160, 160, 96, 1, 2, 0, 2, 10, 6, 0, ("glds", "64x128", "split=0", "ntail=1", "mtail=1"), None),
-    (160, 160, 96, 1, 2, 0, 2, 10, 6, 5, ("glds", "64x128", "split=1", "short=1", "ntail=1", "mtail=1"),
-     "splitk_reduce4"),
-    # the non-FAST gather (Cin % 32 != 0, padded input channels) with 16-bit operands
-    (20, 24, 70, 3, 1, 1, 2, 7, 6, 0, ("igemm", "64x64x32", "fast=0", "split=0", "ntail=1", "mtail=1"), None),
-]
-
-
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("cin,ldx,cout,k,s,p,B,H,W,split_k,plan,reduce", IGEMM_EDGES)
+@pytest.mark.parametrize("cin,ldx,cout,k,s,p,B,H,W,split_k,plan,reduce", conv_cases.IGEMM_EDGES)
 def test_igemm_edge_plans(lib, dt, cin, ldx, cout, k, s, p, B, H, W, split_k, plan, reduce):
     from ghost_amd import _lib
     from ghost_amd.network.pack import pack_conv, rup
@@ -451,7 +417,7 @@ def test_igemm_edge_plans(lib, dt, cin, ldx, cout, k, s, p, B, H, W, split_k, pl
     xin[..., :cin] = x.permute(0, 2, 3, 1)
     xd = xin.to(dt).to(DEV)
     wp = pack_conv(w, dt).to(DEV)
-    ldy = cout + 8
+    ldy = cout + conv_cases.IGEMM_LDY_PAD
     y = torch.full((B, Ho, Wo, ldy), float("nan"), dtype=dt, device=DEV)
     y[..., cout:] = SENTINEL
     scp = torch.zeros(rup(cout, 128), device=DEV); scp[:cout] = sc.to(DEV)
@@ -465,7 +431,7 @@ def test_igemm_edge_plans(lib, dt, cin, ldx, cout, k, s, p, B, H, W, split_k, pl
     got = y.float().cpu()
     assert torch.all(got[..., cout:] == SENTINEL), "wrote outside its channel slice"
     _ulp_gate(got[..., :cout].permute(0, 3, 1, 2), ref, dt)
-    _assert_plan(sigs, plan + ("t=" + ("bf16" if dt == torch.bfloat16 else "f16"),) if plan[0] == "glds" else plan)
+    _assert_plan(sigs, conv_cases.gemm_tokens(plan, "bf16" if dt == torch.bfloat16 else "f16"))
     if reduce:
         _assert_plan(sigs, (reduce,))
     else:
@@ -473,16 +439,13 @@ def test_igemm_edge_plans(lib, dt, cin, ldx, cout, k, s, p, B, H, W, split_k, pl
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("cout,plan", [
-    (64, ("igemm", "256x64x32", "kind=T4S2", "split=1", "ragged=1", "mtail=1")),
-    (128, ("glds", "64x128", "kind=T4S2", "split=1", "ragged=1", "mtail=1")),
-])
+@pytest.mark.parametrize("cout,plan", conv_cases.CONVT_EDGES)
 def test_convT_igemm_edge_plans(lib, dt, cout, plan):
     """ConvT 4x4/s2 544 -> Cout at B = 1, 4 x 6 (M = 24 per parity class, nk = 68): the heuristic's 8 splits are
     seven of 9 K steps and a last of 5.  The slice and sentinel layout of test_convT_op."""
     from ghost_amd import _lib
     from ghost_amd.network.pack import pack_convT4x4, rup
-    cin, H, W = 544, 4, 6
+    cin, H, W = conv_cases.CONVT_CIN, conv_cases.CONVT_H, conv_cases.CONVT_W
     g = torch.Generator().manual_seed(cin + cout)
     x = torch.randn(1, cin, H, W, generator=g)
     w = torch.randn(cin, cout, 4, 4, generator=g) * (2.0 / (cin * 16)) ** 0.5
@@ -491,7 +454,7 @@ def test_convT_igemm_edge_plans(lib, dt, cout, plan):
     ref = F.leaky_relu(F.conv_transpose2d(x.to(dt).double(), w.to(dt).double(), stride=2, padding=1)
                        * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1), 0.1)
     wp = pack_convT4x4(w, dt).to(DEV)
-    ld = cout + 32
+    ld = cout + conv_cases.CONVT_LDY_PAD
     y = torch.full((1, 2 * H, 2 * W, ld), float("nan"), dtype=dt, device=DEV)
     y[..., cout:] = SENTINEL
     scp = torch.zeros(rup(cout, 128), device=DEV); scp[:cout] = sc.to(DEV)
