@@ -36,6 +36,23 @@ struct AadV3Desc {
   unsigned long long* tclk = nullptr;
 };
 
+// what the L layers of a launch share, for an H x W image (up2x: hin is its [B, H/2, W/2] source); the caller
+// sets L, then each layer
+inline AadV3Desc aad_v3_desc(int dt, const void* za, int lda, int Ca, const void* hin, int ldh, const float* stat, int B,
+                             int H, int W, int C, int id_ld, float slope, bool up2x) {
+  AadV3Desc d;
+  d.dt = dt;
+  d.za = za; d.lda = lda; d.Ca = Ca; d.hin = hin; d.ldh = ldh; d.stat = stat;
+  d.B = B; d.HW = H * W; d.C = C; d.id_ld = id_ld; d.slope = slope;
+  if (up2x) { d.up_H = H / 2; d.up_W = W / 2; }
+  return d;
+}
+inline void aad_v3_set_layer(AadV3Desc& d, int l, const void* w3, const float* b3, const float* wh, const float* bh,
+                             const float* idgb, void* out, int ldo) {
+  d.w3[l] = w3; d.b3[l] = b3; d.wh[l] = wh; d.bh[l] = bh; d.idgb[l] = idgb;
+  d.out[l] = out; d.ldo[l] = ldo;
+}
+
 // What a launch of a descriptor runs, decided from its integers and flags alone (dt, B, HW, C, Ca, L, the leading
 // dimensions, up_H / up_W, zwld, slope == 0, which zw[l] are set): no pointer is read through, no HIP call made.
 enum class AadV3Kernel { None, V3, V3Wide, V3Zp1, V3Z, V4, V4Z, V5, V5Z, V5ZAsm, V5Wide };

@@ -23,6 +23,21 @@ struct AadWideDesc {
   int dt = 1;                                  // storage type: GHOST_BF16 (1) or GHOST_F16 (2)
 };
 
+// the inputs of a launch, then its one layer (the same pair as aad_v3.h's)
+inline AadWideDesc aad_wide_desc(int dt, const void* za, int lda, int Ca, const void* hin, int ldh, const float* stat,
+                                 int B, int HW, int C, int id_ld, float slope) {
+  AadWideDesc d;
+  d.dt = dt;
+  d.za = za; d.lda = lda; d.Ca = Ca; d.hin = hin; d.ldh = ldh; d.stat = stat;
+  d.B = B; d.HW = HW; d.C = C; d.id_ld = id_ld; d.slope = slope;
+  return d;
+}
+inline void aad_wide_set_layer(AadWideDesc& d, const void* w3, const float* b3, const float* wh, const float* bh,
+                               const float* idgb, const float* mask, void* out, int ldo) {
+  d.w3 = w3; d.b3 = b3; d.wh = wh; d.bh = bh; d.idgb = idgb; d.mask = mask;
+  d.out = out; d.ldo = ldo;
+}
+
 // What a launch of a descriptor runs, decided from its integers (dt, B, HW, C, Ca, the leading dimensions) and
 // from whether za and w3 are 16-byte aligned (aad_gemm's DMA needs it; without it the launch takes aad_wide)
 enum class AadWideKernel { None, Gemm, Wide, WideDeep };

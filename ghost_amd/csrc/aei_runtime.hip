@@ -26,6 +26,7 @@
 #include "conv_path.h"
 #include "ghost_common.h"
 #include "ops.h"
+#include "plan_ctx.h"
 #include "tap_rows.h"
 
 using namespace ghost;
@@ -36,7 +37,7 @@ static int fail(int rc, const std::string& msg) {
   return rc == 0 ? GHOST_EINVAL : rc;
 }
 namespace ghost {
-// shared with the other runtimes of the library (arc_runtime.hip): one ghost_last_error() per thread
+// shared with the rest of the library (plan_ctx.h): one ghost_last_error() per thread
 int set_last_error(int rc, const std::string& msg) { return fail(rc, msg); }
 int set_last_error(int rc, const char* msg) { return fail(rc, std::string(msg)); }
 }  // namespace ghost
@@ -57,11 +58,137 @@ const int kGenUnet[8][3] = {{1024, 1024, 1024}, {1024, 1024, 2048}, {1024, 1024,
 const int kGenLink[8][3] = {{1024, 1024, 1024}, {1024, 1024, 1024}, {1024, 1024, 512}, {1024, 512, 256},
                             {512, 256, 128},    {256, 128, 64},     {128, 64, 32},     {64, 3, 32}};
 
-inline int rup(int v, int m) { return (v + m - 1) / m * m; }
+// profiling classes: the bits of ghost_aei_profile's mask and ghost_aei_profile_read's index (the values are ABI)
+enum ProfCls {
+  PROF_NONE = -1,
+  PROF_AAD = 0,         // every AAD launch
+  PROF_AAD_UP256 = 1,   // the 256x256 AAD kernel that reads h_in through the upsample
+  PROF_GEN = 2,         // generator convs
+  PROF_GEN256 = 3,      // generator convs at 256x256
+  PROF_STATS = 4,       // statistics and masks
+  PROF_ENC = 5,         // encoder convs
+  PROF_UP = 6,          // upsample
+  PROF_ID = 7,          // identity prologue
+  PROF_NCLS = 8
+};
 
-struct ProfClass {
-  double ms = 0, bytes = 0, flops = 0;
-  int64_t launches = 0;
+// per-class event brackets around launches, folded into class totals after the caller synchronised, and the
+// in-kernel clock of class 1's launches
+struct Profiler {
+  struct Total {
+    double ms = 0, bytes = 0, flops = 0;
+    int64_t launches = 0;
+  };
+  struct Pending { int cls; int e0, e1; double bytes, flops; };
+  int mask = 0;
+  std::vector<hipEvent_t> ev;
+  std::vector<Pending> pend;
+  int ev_used = 0;
+  Total total[PROF_NCLS];
+  // per clocked launch a region of per-workgroup start and per-wave end stamps (AadV3Plan::clock_words); clk_cap
+  // words of device buffer, bump-allocated
+  unsigned long long* clk = nullptr;
+  size_t clk_cap = 0, clk_used = 0;
+  int clk_dev = -1;
+  std::vector<std::pair<size_t, int>> clk_launch;   // (offset, words) per clocked launch
+  int roof_version = 0;                              // kernel generation of class 1's last launch (aad_v3.h)
+
+  ~Profiler() {
+    for (auto e : ev) (void)hipEventDestroy(e);
+    if (clk) (void)hipFree(clk);
+  }
+  bool on(int cls) const { return cls >= 0 && (mask & (1 << cls)); }
+  // opens a bracket on stream s: the index of its event pair, or -1 when the class is not profiled
+  int begin(int cls, hipStream_t s) {
+    if (!on(cls)) return -1;
+    if (ev_used + 2 > (int)ev.size()) {
+      for (int i = 0; i < 64; ++i) {
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return -1;
+        ev.push_back(e);
+      }
+    }
+    const int e0 = ev_used;
+    ev_used += 2;
+    (void)hipEventRecord(ev[e0], s);
+    return e0;
+  }
+  void end(int cls, int e0, hipStream_t s, double bytes, double flops) {
+    if (e0 < 0) return;
+    (void)hipEventRecord(ev[e0 + 1], s);
+    pend.push_back({cls, e0, e0 + 1, bytes, flops});
+  }
+  // the clock region of a launch on device dev (nullptr: not armed there, or the buffer is full)
+  unsigned long long* next_clk(int words, int dev) {
+    if (!clk || clk_dev != dev || words <= 0 || clk_used + (size_t)words > clk_cap) return nullptr;
+    clk_launch.push_back({clk_used, words});
+    unsigned long long* p = clk + clk_used;
+    clk_used += (size_t)words;
+    return p;
+  }
+  // a new measurement of the classes in class_mask; the text of a failure, else nullptr
+  const char* reset(int class_mask) {
+    mask = class_mask;
+    pend.clear();
+    ev_used = 0;
+    for (auto& t : total) t = Total{};
+    clk_used = 0;
+    clk_launch.clear();
+    if (!on(PROF_AAD_UP256)) return nullptr;
+    int dev = -1;   // arm the in-kernel clock (buffer on the current device)
+    if (hipGetDevice(&dev) != hipSuccess) return "hipGetDevice failed";
+    if (clk && clk_dev != dev) {
+      (void)hipFree(clk);
+      clk = nullptr;
+    }
+    if (!clk) {
+      clk_cap = size_t(8) << 20;   // 64 MB: 227 launches of the B = 64 256x256 kernel
+      if (hipMalloc(&clk, sizeof(unsigned long long) * clk_cap) != hipSuccess) {
+        clk = nullptr;
+        return "clock buffer allocation failed";
+      }
+      clk_dev = dev;
+    }
+    return nullptr;
+  }
+  // folds the completed brackets into the class totals (the caller synchronised the streams); a hipError_t
+  int fold() {
+    for (auto& p : pend) {
+      float t = 0.f;
+      hipError_t e = hipEventElapsedTime(&t, ev[p.e0], ev[p.e1]);
+      if (e != hipSuccess) return (int)e;
+      Total& pc = total[p.cls];
+      pc.ms += t;
+      pc.launches += 1;
+      pc.bytes += p.bytes;
+      pc.flops += p.flops;
+    }
+    pend.clear();
+    ev_used = 0;
+    return 0;
+  }
+  // the clocked launches' first start to last end, summed; the text of a failure, else nullptr
+  const char* read_clock(double* us_total, int64_t* launches) {
+    if (!clk || clk_launch.empty()) return nullptr;
+    std::vector<unsigned long long> v(clk_used);
+    if (hipMemcpy(v.data(), clk, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost) != hipSuccess)
+      return "clock buffer read failed";
+    int rate_khz = 0;
+    if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, clk_dev) != hipSuccess || rate_khz <= 0)
+      return "wall clock rate unavailable";
+    double ticks = 0;
+    for (auto& L : clk_launch) {
+      const size_t grid = (size_t)L.second / 9;   // 1 start + 8 wave ends per workgroup
+      unsigned long long t0 = ~0ull, t1 = 0;
+      for (size_t i = 0; i < grid; ++i) t0 = std::min(t0, v[L.first + i]);
+      for (size_t i = grid; i < (size_t)L.second; ++i) t1 = std::max(t1, v[L.first + i]);
+      if (t1 <= t0) continue;
+      ticks += (double)(t1 - t0);
+      ++*launches;
+    }
+    *us_total = ticks / (rate_khz * 1e-3);
+    return nullptr;
+  }
 };
 
 }  // namespace
@@ -70,7 +197,7 @@ struct ghost_aei {
   bool linknet = false;
   bool resnet = false;   // backbone='resnet': MLAttrEncoderResnet (resnet.py:81-149) + the unet generator
   int nb = 2, c_id = 512, dt = GHOST_F32, esz = 4;
-  std::map<std::string, const void*> slots;   // name -> device pointer (nullptr = unbound)
+  Slots slots;
   int id_total = 0;                            // sum over AAD layers of 2*c_x
   // per-handle plan options (ghost_aei_set_option); defaults are the measured choices
   int opt[GHOST_AEI_NOPT] = {1, 1, 1, GHOST_KNOB("GHOST_AAD_ZP", 2), 1};
@@ -86,27 +213,7 @@ struct ghost_aei {
   std::map<int, UpPath> up_path;
   hipEvent_t* zev = nullptr;                   // the events of the device of the running call
   void* taps[8] = {nullptr};                   // ghost_aei_set_taps: AADBlk1..7 outputs copied here
-  // profiling
-  int prof_mask = 0;
-  std::vector<hipEvent_t> ev;
-  struct Pending { int cls; int e0, e1; double bytes, flops; };
-  std::vector<Pending> pend;
-  int ev_used = 0;
-  ProfClass prof[8];
-  // in-kernel clock of the roofline kernel's launches (profiling class 1): per launch a region of per-workgroup
-  // start and per-wave end stamps (AadV3Plan::clock_words); clk_cap words of device buffer, bump-allocated
-  unsigned long long* clk = nullptr;
-  size_t clk_cap = 0, clk_used = 0;
-  int clk_dev = -1;
-  std::vector<std::pair<size_t, int>> clk_launch;   // (offset, words) per clocked launch
-  int roof_version = 0;                        // kernel generation of class 1's last launch (aad_v3.h)
-  unsigned long long* next_clk(int words) {
-    if (!clk || words <= 0 || clk_used + (size_t)words > clk_cap) return nullptr;
-    clk_launch.push_back({clk_used, words});
-    unsigned long long* p = clk + clk_used;
-    clk_used += (size_t)words;
-    return p;
-  }
+  Profiler prof;
 
   typedef int Pair[2];
   typedef int Triple[3];
@@ -129,15 +236,8 @@ namespace {
 constexpr int kSemWords = 4096;                  // arrival counters per stream (16 KB)
 constexpr size_t kSemBytes = 2 * kSemWords * sizeof(unsigned);   // the main and the up-path stream's sets
 
-struct Ctx {
-  ghost_aei* h;
-  bool dry;
-  char* base;
-  size_t off = 0, cap = 0;
-  size_t scratch_need = 0;  // max split-K / IN-stats partial bytes
-  char* scratch = nullptr;
-  size_t scratch_cap = 0;
-  hipStream_t s;
+struct Ctx : PlanCtx {
+  ghost_aei* h = nullptr;
   // two-stream plan: the up path's stream and its own scratch region (the launches of the two streams
   // overlap, so they cannot share the split-K / statistics partials)
   bool dual = false, force_single = false;
@@ -149,59 +249,18 @@ struct Ctx {
   unsigned* sem_main = nullptr;
   unsigned* sem_up = nullptr;
   unsigned* sem() const { return scratch_up && scratch == scratch_up ? sem_up : sem_main; }
-  int rc = 0;
-  std::string where;
-
-  void* alloc(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    void* p = dry ? reinterpret_cast<void*>(uintptr_t(0x10000000) + off) : base + off;
-    off += bytes;
-    return p;
-  }
-  bool ok() const { return rc == 0; }
-  void check(int r, const char* what) {
-    if (r != 0 && rc == 0) {
-      rc = r;
-      where = what;
-    }
-  }
-  const void* W(const std::string& name) {
-    auto it = h->slots.find(name);
-    if (dry) {  // sizing needs no weights, but every slot the plan reads must be declared
-      if (it == h->slots.end() && rc == 0) {
-        rc = GHOST_EINVAL;
-        where = "plan reads undeclared slot " + name;
-      }
-      return reinterpret_cast<const void*>(uintptr_t(0x1000));
-    }
-    if (it == h->slots.end() || !it->second) {
-      if (rc == 0) {
-        rc = GHOST_ENOTREADY;
-        where = "unbound weight slot " + name;
-      }
-      return nullptr;
-    }
-    return it->second;
-  }
-  // profiling brackets
-  int prof_begin(int cls) {
-    if (dry || !(h->prof_mask & (1 << cls))) return -1;
-    if (h->ev_used + 2 > (int)h->ev.size()) {
-      for (int i = 0; i < 64; ++i) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return -1;
-        h->ev.push_back(e);
-      }
-    }
-    int e0 = h->ev_used;
-    h->ev_used += 2;
-    (void)hipEventRecord(h->ev[e0], s);
-    return e0;
-  }
-  void prof_end(int cls, int e0, double bytes, double flops) {
-    if (e0 < 0) return;
-    (void)hipEventRecord(h->ev[e0 + 1], s);
-    h->pend.push_back({cls, e0, e0 + 1, bytes, flops});
+  const void* W(const std::string& name) { return PlanCtx::W(h->slots, name); }
+  // one launch of the real run: fn() launches and returns its status.  Bracketed for class cls and, inside it,
+  // cls_big (PROF_NONE: no second bracket); bytes and flops are the launch's share of both classes' totals
+  template <class F>
+  void launch(int cls, int cls_big, double bytes, double flops, const char* what, F fn) {
+    if (!ok() || dry) return;
+    Profiler& p = h->prof;
+    const int e = p.begin(cls, s);
+    const int e_big = p.begin(cls_big, s);
+    check(fn(), what);
+    p.end(cls_big, e_big, s, bytes, flops);
+    p.end(cls, e, s, bytes, flops);
   }
 };
 
@@ -209,67 +268,42 @@ struct Ctx {
 static const bool g_trace = GHOST_KNOB("GHOST_PLAN_TRACE", 0) != 0;   // one stderr line per launch (tuning builds)
 
 void run_conv(Ctx& c, ConvDesc& d, int cls_all, int cls_big, double flops) {
-  if (!c.ok()) return;
-  if (c.dry) {
-    size_t need = conv_workspace_bytes(d);
-    if (need > c.scratch_need) c.scratch_need = need;
-    return;
-  }
+  if (c.dry) c.need_scratch(conv_workspace_bytes(d));
+  if (!c.ok() || c.dry) return;
   if (g_trace)
     fprintf(stderr, "[plan] conv%s %dx%d/s%d %dx%d %d->%d epi=%d res=%d %.1f GFLOP\n",
             d.kind == CONV_T4S2 ? "T" : "", d.kh, d.kw, d.stride, d.Hi, d.Wi, d.Cin, d.N, (int)d.epi, d.res != nullptr,
             flops / 1e9);
   const bool big = d.Hi == 256 || d.Hi * (d.kind == CONV_T4S2 ? 2 : 1) == 256;
-  int e_all = c.prof_begin(cls_all);
-  int e_big = (big && cls_big >= 0) ? c.prof_begin(cls_big) : -1;
   d.sem = c.sem();
   d.nsem = d.sem ? kSemWords : 0;
-  c.check(conv_launch(d, c.scratch, c.scratch_cap, c.s), "conv_launch");
-  double bytes = 0;
-  if (d.epi == EPI_AAD) {
-    // algorithmic AAD bytes: |h_in| + |z_attr| + |out|
-    const double P = (double)d.B * d.Hi * d.Wi;
-    bytes = P * (2.0 * d.C_aad + d.Cin) * (double)c.h->esz;
-  }
-  if (e_big >= 0) c.prof_end(cls_big, e_big, bytes, flops);
-  if (e_all >= 0) c.prof_end(cls_all, e_all, bytes, flops);
+  // algorithmic AAD bytes: |h_in| + |z_attr| + |out|
+  const double bytes = d.epi == EPI_AAD ? (double)d.B * d.Hi * d.Wi * (2.0 * d.C_aad + d.Cin) * (double)c.h->esz : 0;
+  c.launch(cls_all, big ? cls_big : PROF_NONE, bytes, flops, "conv_launch",
+           [&] { return conv_launch(d, c.scratch, c.scratch_cap, c.s); });
 }
 
 void run_stats(Ctx& c, const void* x, int ldx, int B, int HW, int C, float* stat) {
-  if (!c.ok()) return;
-  if (c.dry) {
-    size_t need = in_stats_workspace_bytes(B, HW, C);
-    if (need > c.scratch_need) c.scratch_need = need;
-    return;
-  }
-  int e = c.prof_begin(4);
+  if (c.dry) c.need_scratch(in_stats_workspace_bytes(B, HW, C));
   unsigned* sem = c.sem();
-  c.check(in_stats(c.h->dt, x, ldx, B, HW, C, stat, c.scratch, c.scratch_cap, c.s, sem, sem ? kSemWords : 0),
-          "in_stats");
-  c.prof_end(4, e, (double)B * HW * C * c.h->esz, 0);
+  c.launch(PROF_STATS, PROF_NONE, (double)B * HW * C * c.h->esz, 0, "in_stats", [&] {
+    return in_stats(c.h->dt, x, ldx, B, HW, C, stat, c.scratch, c.scratch_cap, c.s, sem, sem ? kSemWords : 0);
+  });
 }
 
 // statistics of upsample2x(x) for an [B, H, W, C] source, without materialising it
 void run_stats_up(Ctx& c, const void* x, int ldx, int B, int H, int W, int C, float* stat) {
-  if (!c.ok()) return;
-  if (c.dry) {
-    size_t need = in_stats_workspace_bytes(B, 4 * H * W, C);
-    if (need > c.scratch_need) c.scratch_need = need;
-    return;
-  }
-  int e = c.prof_begin(4);
+  if (c.dry) c.need_scratch(in_stats_workspace_bytes(B, 4 * H * W, C));
   unsigned* sem = c.sem();
-  c.check(in_stats_up2x(c.h->dt, x, ldx, B, H, W, C, stat, c.scratch, c.scratch_cap, c.s, sem, sem ? kSemWords : 0),
-          "in_stats_up2x");
-  c.prof_end(4, e, (double)B * H * W * C * c.h->esz, 0);
+  c.launch(PROF_STATS, PROF_NONE, (double)B * H * W * C * c.h->esz, 0, "in_stats_up2x", [&] {
+    return in_stats_up2x(c.h->dt, x, ldx, B, H, W, C, stat, c.scratch, c.scratch_cap, c.s, sem, sem ? kSemWords : 0);
+  });
 }
 
 void run_mask(Ctx& c, const void* x, int ldx, int B, int HW, int C, const float* stat, const float* wh,
               const float* bh, float* mask) {
-  if (!c.ok() || c.dry) return;
-  int e = c.prof_begin(4);
-  c.check(aad_mask(c.h->dt, x, ldx, B, HW, C, stat, wh, bh, mask, c.s), "aad_mask");
-  c.prof_end(4, e, (double)B * HW * C * c.h->esz, 0);
+  c.launch(PROF_STATS, PROF_NONE, (double)B * HW * C * c.h->esz, 0, "aad_mask",
+           [&] { return aad_mask(c.h->dt, x, ldx, B, HW, C, stat, wh, bh, mask, c.s); });
 }
 
 // small images (2x2 .. 8x8): statistics + the masks of the AADLayers named in `ls` (<= 2) in one launch
@@ -281,18 +315,14 @@ void run_stats_masks(Ctx& c, const void* x, int ldx, int B, int HW, int C, float
     wh[l] = (const float*)c.W(ls[l] + ".wh");
     bh[l] = (const float*)c.W(ls[l] + ".bh");
   }
-  if (!c.ok() || c.dry) return;
-  int e = c.prof_begin(4);
-  c.check(stats_mask_small(c.h->dt, x, ldx, B, HW, C, stat, wh[0], bh[0], masks[0], wh[1], bh[1], masks[1], c.s),
-          "stats_mask_small");
-  c.prof_end(4, e, (double)B * HW * C * c.h->esz, 0);
+  c.launch(PROF_STATS, PROF_NONE, (double)B * HW * C * c.h->esz, 0, "stats_mask_small", [&] {
+    return stats_mask_small(c.h->dt, x, ldx, B, HW, C, stat, wh[0], bh[0], masks[0], wh[1], bh[1], masks[1], c.s);
+  });
 }
 
 void run_up(Ctx& c, const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C) {
-  if (!c.ok() || c.dry) return;
-  int e = c.prof_begin(6);
-  c.check(upsample2x(c.h->dt, x, ldx, y, ldy, B, H, W, C, c.s), "upsample2x");
-  c.prof_end(6, e, (double)B * H * W * C * 5 * c.h->esz, 0);
+  c.launch(PROF_UP, PROF_NONE, (double)B * H * W * C * 5 * c.h->esz, 0, "upsample2x",
+           [&] { return upsample2x(c.h->dt, x, ldx, y, ldy, B, H, W, C, c.s); });
 }
 
 // ---------------------------------------------------------------------------
@@ -307,19 +337,13 @@ struct Buf {
 void res_conv(Ctx& c, const std::string& name, const void* x, int ldx, int B, int H, int Cin, int Cout, int k,
               int stride, void* y, int ldy, bool relu, const void* res = nullptr, int ldres = 0) {
   ghost_aei* h = c.h;
-  ConvDesc d;
-  d.ti = d.to = h->dt;
-  d.x = x; d.B = B; d.Hi = H; d.Wi = H; d.Cin = Cin; d.ldx = ldx;
-  d.w = c.W(name + ".w");
-  d.N = Cout; d.Npad = rup(Cout, 128); d.Kpad = rup(k * k * Cin, 32);
-  d.kind = CONV_FWD; d.kh = d.kw = k; d.stride = stride; d.pad = k / 2;
-  d.y = y; d.ldy = ldy;
+  ConvDesc d = conv_desc(h->dt, h->dt, x, B, H, Cin, ldx, c.W(name + ".w"), Cout, CONV_FWD, k, stride, k / 2, y, ldy);
   d.scale = (const float*)c.W(name + ".scale");
   d.shift = (const float*)c.W(name + ".shift");
   d.slope = relu ? 0.f : 1.f;
   if (res) { d.res = res; d.ldres = ldres; d.res_first = 1; }
   const double Ho = (H + 2 * (k / 2) - k) / stride + 1;
-  run_conv(c, d, 5, -1, 2.0 * B * Ho * Ho * Cout * k * k * Cin);
+  run_conv(c, d, PROF_ENC, PROF_NONE, 2.0 * B * Ho * Ho * Cout * k * k * Cin);
 }
 
 // MLAttrEncoderResnet = ResNet(Bottleneck, [2]*6) (resnet.py:81-149): returns
@@ -387,18 +411,13 @@ void encoder(Ctx& c, const void* xin, int B, void* const attr[8]) {
   for (int i = 1; i <= 7; ++i) {
     const int ci = kEncDown[i - 1][0], co = kEncDown[i - 1][1];
     Buf out = i <= 6 ? feat[i] : Buf{attr[0], 1024};
-    ConvDesc d;
-    d.ti = d.to = h->dt;
-    d.x = in.p; d.B = B; d.Hi = Hs; d.Wi = Hs; d.Cin = ci; d.ldx = in.ld;
-    d.w = c.W("enc.conv" + std::to_string(i) + ".w");
-    d.N = co; d.Npad = rup(co, 128); d.Kpad = rup(16 * ci, 32);
-    d.kind = CONV_FWD; d.kh = d.kw = 4; d.stride = 2; d.pad = 1;
-    d.y = out.p; d.ldy = out.ld;
-    d.scale = (const float*)c.W("enc.conv" + std::to_string(i) + ".scale");
-    d.shift = (const float*)c.W("enc.conv" + std::to_string(i) + ".shift");
+    const std::string name = "enc.conv" + std::to_string(i);
+    ConvDesc d = conv_desc(h->dt, h->dt, in.p, B, Hs, ci, in.ld, c.W(name + ".w"), co, CONV_FWD, 4, 2, 1, out.p, out.ld);
+    d.scale = (const float*)c.W(name + ".scale");
+    d.shift = (const float*)c.W(name + ".shift");
     d.slope = kBnLrelu;
     const double Ho = Hs / 2;
-    run_conv(c, d, 5, -1, 2.0 * B * Ho * Ho * co * 16.0 * ci);
+    run_conv(c, d, PROF_ENC, PROF_NONE, 2.0 * B * Ho * Ho * co * 16.0 * ci);
     in = out;
     Hs /= 2;
   }
@@ -419,18 +438,13 @@ void encoder(Ctx& c, const void* xin, int B, void* const attr[8]) {
     h->attr_geom(i, Cin, H);
     h->attr_geom(i + 1, Cout, Ho);
     const int co = h->up()[i - 1][1];
-    ConvDesc d;
-    d.ti = d.to = h->dt;
-    d.x = attr[i - 1]; d.B = B; d.Hi = H; d.Wi = H; d.Cin = Cin; d.ldx = Cin;
-    d.w = c.W("enc.deconv" + std::to_string(i) + ".w");
-    d.N = co; d.Npad = rup(co, 128); d.Kpad = rup(4 * Cin, 32);
-    d.kind = CONV_T4S2;
-    d.y = attr[i]; d.ldy = Cout;
-    d.scale = (const float*)c.W("enc.deconv" + std::to_string(i) + ".scale");
-    d.shift = (const float*)c.W("enc.deconv" + std::to_string(i) + ".shift");
+    const std::string name = "enc.deconv" + std::to_string(i);
+    ConvDesc d = conv_desc(h->dt, h->dt, attr[i - 1], B, H, Cin, Cin, c.W(name + ".w"), co, CONV_T4S2, 1, 1, 0, attr[i], Cout);
+    d.scale = (const float*)c.W(name + ".scale");
+    d.shift = (const float*)c.W(name + ".shift");
     d.slope = kBnLrelu;
     if (h->linknet) { d.res = feat[7 - i].p; d.ldres = feat[7 - i].ld; }
-    run_conv(c, d, 5, -1, 2.0 * B * Ho * Ho * co * 4.0 * Cin);
+    run_conv(c, d, PROF_ENC, PROF_NONE, 2.0 * B * Ho * Ho * co * 4.0 * Cin);
     if (dual && c.ok()) c.check((int)hipEventRecord(h->zev[i + 1], c.s), "event record");
   }
   int C7, H7, C8, H8;
@@ -465,14 +479,10 @@ void aad(Ctx& c, const std::string& name, const void* hin, int ldh, const float*
   const float* wh = (const float*)c.W(name + ".wh");
   const float* bh = (const float*)c.W(name + ".bh");
   if (fused) {
-    if (!c.ok() || c.dry) return;
-    int e_all = c.prof_begin(0);
-    int e_big = -1;
-    c.check(aad_fused(h->dt, za, lda, Ca, gbw, rup(Ca, 32), gbb, hin, ldh, stat, wh, bh, idgb + id_off, h->id_total,
-                      out, ldo, B, n * n, C, 0.0f, c.s),
-            "aad_fused");
-    if (e_big >= 0) c.prof_end(1, e_big, bytes, flops);
-    if (e_all >= 0) c.prof_end(0, e_all, bytes, flops);
+    c.launch(PROF_AAD, PROF_NONE, bytes, flops, "aad_fused", [&] {
+      return aad_fused(h->dt, za, lda, Ca, gbw, rup(Ca, 32), gbb, hin, ldh, stat, wh, bh, idgb + id_off, h->id_total,
+                       out, ldo, B, n * n, C, 0.0f, c.s);
+    });
     return;
   }
   const float* mask = pre_mask;
@@ -481,19 +491,13 @@ void aad(Ctx& c, const std::string& name, const void* hin, int ldh, const float*
     run_mask(c, hin, ldh, B, n * n, C, stat, wh, bh, m);
     mask = m;
   }
-  ConvDesc d;
-  d.ti = d.to = h->dt;
-  d.x = za; d.B = B; d.Hi = n; d.Wi = n; d.Cin = Ca; d.ldx = lda;
-  d.w = gbw;
-  d.N = 2 * C; d.Npad = rup(2 * C, 128); d.Kpad = rup(Ca, 32);
-  d.kind = CONV_FWD; d.kh = d.kw = 1; d.stride = 1; d.pad = 0;
-  d.y = out; d.ldy = ldo;
+  ConvDesc d = conv_desc(h->dt, h->dt, za, B, n, Ca, lda, gbw, 2 * C, CONV_FWD, 1, 1, 0, out, ldo);
   d.shift = gbb;
   d.slope = 0.0f;  // the ReLU that follows every AADLayer in AddBlocksSequential
   d.epi = EPI_AAD;
   d.hin = hin; d.ldh = ldh; d.stat = stat;
   d.idgb = idgb ? idgb + id_off : nullptr; d.id_ld = h->id_total; d.mask = mask; d.C_aad = C;
-  run_conv(c, d, 0, -1, flops);
+  run_conv(c, d, PROF_AAD, PROF_NONE, flops);
 }
 
 struct AadOut {
@@ -536,12 +540,9 @@ void aad_group(Ctx& c, const std::vector<AadOut>& ls, const void* hin, int ldh, 
       const float* bh0 = (const float*)c.W(ls[0].name + ".bh");
       const float* wh1 = ls.size() > 1 ? (const float*)c.W(ls[1].name + ".wh") : nullptr;
       const float* bh1 = ls.size() > 1 ? (const float*)c.W(ls[1].name + ".bh") : nullptr;
-      if (c.ok() && !c.dry) {
-        int e = c.prof_begin(4);
-        c.check(aad_mask2(h->dt, hin, ldh, B, n * n, C, stat, wh0, bh0, masks[0], wh1, bh1, masks[1], c.s),
-                "aad_mask2");
-        c.prof_end(4, e, (double)B * n * n * C * h->esz, 0);
-      }
+      c.launch(PROF_STATS, PROF_NONE, (double)B * n * n * C * h->esz, 0, "aad_mask2", [&] {
+        return aad_mask2(h->dt, hin, ldh, B, n * n, C, stat, wh0, bh0, masks[0], wh1, bh1, masks[1], c.s);
+      });
     }
     for (size_t li = 0; li < ls.size(); ++li) {
       const AadOut& l = ls[li];
@@ -550,22 +551,16 @@ void aad_group(Ctx& c, const std::vector<AadOut>& ls, const void* hin, int ldh, 
             pre_masks ? pre_masks[li] : nullptr);
         continue;
       }
-      AadWideDesc d;
-      d.dt = h->dt;
-      d.za = za; d.lda = lda; d.Ca = Ca; d.hin = hin; d.ldh = ldh; d.stat = stat;
-      d.B = B; d.HW = n * n; d.C = C; d.id_ld = h->id_total; d.slope = 0.0f;   // + the ReLU that follows
-      d.w3 = c.W(l.name + ".w3");
-      d.b3 = (const float*)c.W(l.name + ".b3");
-      d.wh = (const float*)c.W(l.name + ".wh");
-      d.bh = (const float*)c.W(l.name + ".bh");
-      d.idgb = idgb ? idgb + l.id_off : nullptr;
-      d.out = l.out; d.ldo = l.ldo;
-      d.mask = masks[li];
-      if (!c.ok() || c.dry) continue;
+      // slope 0: the ReLU that follows the layer
+      AadWideDesc d = aad_wide_desc(h->dt, za, lda, Ca, hin, ldh, stat, B, n * n, C, h->id_total, 0.0f);
+      const void* w3 = c.W(l.name + ".w3");
+      const float* b3 = (const float*)c.W(l.name + ".b3");
+      const float* wh = (const float*)c.W(l.name + ".wh");
+      const float* bh = (const float*)c.W(l.name + ".bh");
+      aad_wide_set_layer(d, w3, b3, wh, bh, idgb ? idgb + l.id_off : nullptr, masks[li], l.out, l.ldo);
       const double Pn = (double)B * n * n;
-      int e_all = c.prof_begin(0);
-      c.check(aad_wide(d, c.s), "aad_wide");
-      if (e_all >= 0) c.prof_end(0, e_all, Pn * (2.0 * C + Ca) * h->esz, 2.0 * Pn * 2.0 * C * Ca);
+      c.launch(PROF_AAD, PROF_NONE, Pn * (2.0 * C + Ca) * h->esz, 2.0 * Pn * 2.0 * C * Ca, "aad_wide",
+               [&] { return aad_wide(d, c.s); });
     }
     return;
   }
@@ -574,45 +569,38 @@ void aad_group(Ctx& c, const std::vector<AadOut>& ls, const void* hin, int ldh, 
   static const int pair128 = GHOST_KNOB("GHOST_AAD_PAIR128", 1);
   const size_t lmax = (C == 128 && !pair128) ? 1 : (size_t)aad_v3_max_layers(C, Ca);
   for (size_t i0 = 0; i0 < ls.size(); i0 += lmax) {
-    AadV3Desc d;
-    d.dt = h->dt;
-    d.za = za; d.lda = lda; d.Ca = Ca; d.hin = hin; d.ldh = ldh; d.stat = stat;
-    d.B = B; d.HW = n * n; d.C = C; d.id_ld = h->id_total; d.slope = 0.0f;   // + the ReLU that follows
+    // slope 0: the ReLU that follows the layers
+    AadV3Desc d = aad_v3_desc(h->dt, za, lda, Ca, hin, ldh, stat, B, n, n, C, h->id_total, 0.0f, up_src);
     d.L = (int)std::min(lmax, ls.size() - i0);
-    if (up_src) d.up_H = d.up_W = n / 2;
     for (int l = 0; l < d.L; ++l) {
       const AadOut& o = ls[i0 + l];
-      d.w3[l] = c.W(o.name + ".w3");
-      d.b3[l] = (const float*)c.W(o.name + ".b3");
-      d.wh[l] = (const float*)c.W(o.name + ".wh");
-      d.bh[l] = (const float*)c.W(o.name + ".bh");
-      d.idgb[l] = idgb ? idgb + o.id_off : nullptr;
-      d.out[l] = o.out;
-      d.ldo[l] = o.ldo;
+      const void* w3 = c.W(o.name + ".w3");
+      const float* b3 = (const float*)c.W(o.name + ".b3");
+      const float* wh = (const float*)c.W(o.name + ".wh");
+      const float* bh = (const float*)c.W(o.name + ".bh");
+      aad_v3_set_layer(d, l, w3, b3, wh, bh, idgb ? idgb + o.id_off : nullptr, o.out, o.ldo);
       d.zw[l] = o.zw;
       if (o.zw) d.zwld = o.zwld;
     }
-    if (!c.ok() || c.dry) continue;
     const double Pn = (double)B * n * n;
     // algorithmic bytes by SURVEY.md §8d's formula, fixed regardless of fusion:
     // sum over the L AADLayers of |h_in| + |z_attr| + |out| (PMC traffic shows what fusion saves)
     const double bytes = Pn * (double)d.L * (2.0 * C + Ca) * h->esz;
     const double flops = 2.0 * Pn * 2.0 * C * Ca * d.L;
-    if (g_trace)
-      fprintf(stderr, "[plan] aad_v3 %dx%d C=%d Ca=%d L=%d up=%d\n", n, n, C, Ca, d.L, (int)up_src);
-    int e_all = c.prof_begin(0);
     // class 1: the block-input AAD kernel at 256x256 (reads h_in through the x2 upsample; one or two layers)
-    int e_big = (n == 256 && up_src) ? c.prof_begin(1) : -1;
-    // only the v4 / v5 kernels write clock stamps: a generation-3 plan has no clock words and reserves no region,
-    // so ghost_aei_profile_clock never reads unwritten words
-    const AadV3Plan p = aad_v3_plan(d);
-    if (e_big >= 0) {
-      h->roof_version = p.version;
-      if (h->clk_dev == c.dev) d.tclk = h->next_clk(p.clock_words);
-    }
-    c.check(aad_v3(d, p, c.s), "aad_v3");
-    if (e_big >= 0) c.prof_end(1, e_big, bytes, flops);
-    if (e_all >= 0) c.prof_end(0, e_all, bytes, flops);
+    const bool big = n == 256 && up_src;
+    c.launch(PROF_AAD, big ? PROF_AAD_UP256 : PROF_NONE, bytes, flops, "aad_v3", [&] {
+      if (g_trace)
+        fprintf(stderr, "[plan] aad_v3 %dx%d C=%d Ca=%d L=%d up=%d\n", n, n, C, Ca, d.L, (int)up_src);
+      // only the v4 / v5 kernels write clock stamps: a generation-3 plan has no clock words and reserves no
+      // region, so ghost_aei_profile_clock never reads unwritten words
+      const AadV3Plan p = aad_v3_plan(d);
+      if (big && h->prof.on(PROF_AAD_UP256)) {
+        h->prof.roof_version = p.version;
+        d.tclk = h->prof.next_clk(p.clock_words, c.dev);
+      }
+      return aad_v3(d, p, c.s);
+    });
   }
 }
 
@@ -622,33 +610,21 @@ bool conv3x3(Ctx& c, const std::string& wname, const void* x, int ldx, int Cin, 
   const double flops = 2.0 * B * n * n * Cout * 9.0 * Cin;
   if (Cout <= 3 && conv3x3_narrow_supported(c.h->dt, n, n, Cin, ldx, Cout)) {
     const void* wn = c.W(wname + "n");   // "...conv{i}.w" + "n" = the narrow layout slot
-    if (!c.ok() || c.dry) return false;
-    int e_all = c.prof_begin(2);
-    int e_big = n == 256 ? c.prof_begin(3) : -1;
-    c.check(conv3x3_narrow(c.h->dt, x, B, n, n, Cin, ldx, wn, rup(Cin, 32), Cout, res, ldres, tanh_out, y, ldy, u8, c.s),
-            "conv3x3_narrow");
-    if (e_big >= 0) c.prof_end(3, e_big, 0, flops);
-    if (e_all >= 0) c.prof_end(2, e_all, 0, flops);
+    c.launch(PROF_GEN, n == 256 ? PROF_GEN256 : PROF_NONE, 0, flops, "conv3x3_narrow", [&] {
+      return conv3x3_narrow(c.h->dt, x, B, n, n, Cin, ldx, wn, rup(Cin, 32), Cout, res, ldres, tanh_out, y, ldy, u8, c.s);
+    });
     return false;
   }
-  ConvDesc d;
-  d.ti = d.to = c.h->dt;
-  d.x = x; d.B = B; d.Hi = n; d.Wi = n; d.Cin = Cin; d.ldx = ldx;
-  d.w = c.W(wname);
-  d.N = Cout; d.Npad = rup(Cout, 128); d.Kpad = rup(9 * Cin, 32);
-  d.kind = CONV_FWD; d.kh = d.kw = 3; d.stride = 1; d.pad = 1;
-  d.y = y; d.ldy = ldy;
+  ConvDesc d = conv_desc(c.h->dt, c.h->dt, x, B, n, Cin, ldx, c.W(wname), Cout, CONV_FWD, 3, 1, 1, y, ldy);
   d.res = res; d.ldres = ldres;
   d.tanh_out = tanh_out; d.u8 = u8;
   int nrec = 0;
   const bool fused = stat && c.h->opt[GHOST_AEI_OPT_FUSE_STATS] && conv3x3_pp_takes(d, &nrec);
   if (fused) d.in_part = (float*)c.alloc((size_t)B * nrec * Cout * 2 * sizeof(float));
-  run_conv(c, d, 2, 3, flops);
-  if (fused && c.ok() && !c.dry) {
-    int e = c.prof_begin(4);
-    c.check(in_stats_from_tiles(d.in_part, B, nrec, Cout, stat, c.s), "in_stats_from_tiles");
-    c.prof_end(4, e, 0, 0);
-  }
+  run_conv(c, d, PROF_GEN, PROF_GEN256, flops);
+  if (fused)
+    c.launch(PROF_STATS, PROF_NONE, 0, 0, "in_stats_from_tiles",
+             [&] { return in_stats_from_tiles(d.in_part, B, nrec, Cout, stat, c.s); });
   return fused;
 }
 
@@ -665,28 +641,16 @@ GenIn generator_prologue(Ctx& c, int B, const float* zid32, float* idgb_out = nu
   const int es = h->esz;
   // identity projections of every AADLayer at once: idgb[b] = [gamma_id | beta_id] per layer (fc1/fc2)
   float* idgb = idgb_out ? idgb_out : (float*)c.alloc((size_t)B * h->id_total * sizeof(float));
-  {
-    ConvDesc d;
-    d.ti = d.to = GHOST_F32;
-    d.x = zid32; d.B = B; d.Hi = 1; d.Wi = 1; d.Cin = h->c_id; d.ldx = h->c_id;
-    d.w = c.W("gen.id.w");
-    d.N = h->id_total; d.Npad = rup(h->id_total, 128); d.Kpad = rup(h->c_id, 32);
-    d.y = idgb; d.ldy = h->id_total;
-    d.shift = (const float*)c.W("gen.id.shift");
-    run_conv(c, d, 7, -1, 2.0 * B * h->id_total * h->c_id);
-  }
+  // a GEMM over z_id: a 1x1 conv on a 1x1 image
+  auto gemm = [&](int to, const std::string& name, int N, void* y) {
+    ConvDesc d = conv_desc(GHOST_F32, to, zid32, B, 1, h->c_id, h->c_id, c.W(name + ".w"), N, CONV_FWD, 1, 1, 0, y, N);
+    d.shift = (const float*)c.W(name + ".shift");
+    run_conv(c, d, PROF_ID, PROF_NONE, 2.0 * B * N * h->c_id);
+  };
+  gemm(GHOST_F32, "gen.id", h->id_total, idgb);
   // m1 = up1(z_id): ConvT k2 on a 1x1 input == GEMM to [B, 2, 2, 1024] (AEI_Net.py:101,123)
   void* m = m_out ? m_out : c.alloc((size_t)B * 4 * 1024 * es);
-  {
-    ConvDesc d;
-    d.ti = GHOST_F32; d.to = h->dt;
-    d.x = zid32; d.B = B; d.Hi = 1; d.Wi = 1; d.Cin = h->c_id; d.ldx = h->c_id;
-    d.w = c.W("gen.up1.w");
-    d.N = 4096; d.Npad = 4096; d.Kpad = rup(h->c_id, 32);
-    d.y = m; d.ldy = 4096;
-    d.shift = (const float*)c.W("gen.up1.shift");
-    run_conv(c, d, 7, -1, 2.0 * B * 4096 * h->c_id);
-  }
+  gemm(h->dt, "gen.up1", 4096, m);
   return {idgb, m};
 }
 
@@ -788,19 +752,13 @@ void generator(Ctx& c, int B, const void* const attr[8], GenIn gin, void* y_out,
       } else if (!split) {
         conv3x3(c, cn, a, cin, cin, B, n, cout, y, cout, m, cin, last_k, last_k ? u8 : nullptr);
       } else if (zp == 2) {
-        if (c.ok() && !c.dry) {
-          int e_all = c.prof_begin(2);
-          c.check(tap_sum3x3(h->dt, zh, zx, B, n, n, y, cout, u8, c.s), "tap_sum3x3");
-          c.prof_end(2, e_all, 0, 0);
-        }
+        c.launch(PROF_GEN, PROF_NONE, 0, 0, "tap_sum3x3",
+                 [&] { return tap_sum3x3(h->dt, zh, zx, B, n, n, y, cout, u8, c.s); });
       } else if (zp == 1) {
-        if (c.ok() && !c.dry) {
-          int e_all = c.prof_begin(2);
-          c.check(conv3x3_narrow(h->dt, xq, B, n, n, cin, cin, wn + (size_t)cin * h->esz, wnld, cout, nullptr, 0, 1, y, cout, u8, c.s,
-                                 zh),
-                  "conv3x3_narrow + tap partials");
-          c.prof_end(2, e_all, 0, 2.0 * P * cout * 9.0 * cin);
-        }
+        c.launch(PROF_GEN, PROF_NONE, 0, 2.0 * P * cout * 9.0 * cin, "conv3x3_narrow + tap partials", [&] {
+          return conv3x3_narrow(h->dt, xq, B, n, n, cin, cin, wn + (size_t)cin * h->esz, wnld, cout, nullptr, 0, 1, y,
+                                cout, u8, c.s, zh);
+        });
       } else {
         conv3x3(c, cn, cat, 2 * cin, 2 * cin, B, n, cout, y, cout, nullptr, 0, last_k, last_k ? u8 : nullptr);
       }
@@ -838,9 +796,7 @@ void generator(Ctx& c, int B, const void* const attr[8], GenIn gin, void* y_out,
 
 int check_handle(ghost_aei* h) {
   if (!h) return fail(GHOST_EINVAL, "null handle");
-  for (auto& kv : h->slots)
-    if (!kv.second) return fail(GHOST_ENOTREADY, "unbound weight slot " + kv.first);
-  return 0;
+  return count_missing(h->slots) ? GHOST_ENOTREADY : 0;
 }
 
 void declare_slots(ghost_aei* h) {
@@ -907,7 +863,7 @@ struct Io {
 };
 
 // the identity table's layout: [n][id_total] fp32 gamma_id/beta_id rows (256-aligned block), then [n][4096] m1 rows
-size_t table_idgb_bytes(const ghost_aei* h, int n) { return ((size_t)n * h->id_total * 4 + 255) & ~size_t(255); }
+size_t table_idgb_bytes(const ghost_aei* h, int n) { return align_up((size_t)n * h->id_total * 4); }
 size_t table_bytes(const ghost_aei* h, int n) { return table_idgb_bytes(h, n) + (size_t)n * 4096 * h->esz; }
 
 void plan(Ctx& c, Mode mode, int B, Io io) {
@@ -950,13 +906,11 @@ void plan(Ctx& c, Mode mode, int B, Io io) {
       // GEMMs); the same allocations as the projecting prologue, so the swap workspace size covers both
       gin.idgb = (float*)c.alloc((size_t)B * h->id_total * sizeof(float));
       gin.m = c.alloc((size_t)B * 4 * 1024 * es);
-      if (c.dry || !c.ok()) return;
       const void* tab[2] = {io.table, (const char*)io.table + table_idgb_bytes(h, io.n_ident)};
       const int64_t rb[2] = {(int64_t)h->id_total * 4, (int64_t)4096 * es};
       void* outs[2] = {gin.idgb, gin.m};
-      int e = c.prof_begin(7);
-      c.check(gather_identity_rows(2, tab, rb, outs, io.n_ident, io.idx, B, c.s), "gather_identity_rows");
-      c.prof_end(7, e, (double)B * (rb[0] + rb[1]) * 2, 0);
+      c.launch(PROF_ID, PROF_NONE, (double)B * (rb[0] + rb[1]) * 2, 0, "gather_identity_rows",
+               [&] { return gather_identity_rows(2, tab, rb, outs, io.n_ident, io.idx, B, c.s); });
       return;
     }
     if (!c.dry && c.ok()) c.check(rows_to_f32(io.zid_dtype, io.zid, io.zid_rs, B, h->c_id, zid32, c.s), "rows_to_f32");
@@ -1010,8 +964,7 @@ int64_t plan_bytes(ghost_aei* h, Mode mode, int B) {
   if (mode == M_IDTABLE) io.table = (void*)(fake + 0x2000000);
   plan(c, mode, B, io);
   if (!c.ok()) return (int64_t)c.rc;
-  const size_t scr = (c.scratch_need + 255) & ~size_t(255);
-  return (int64_t)(((c.off + 255) & ~size_t(255)) + kMainSlack + kSemBytes + (c.dual ? 2 : 1) * scr + 256);
+  return (int64_t)(align_up(c.off) + kMainSlack + kSemBytes + (c.dual ? 2 : 1) * align_up(c.scratch_need) + 256);
 }
 
 // The up-path stream of device `dev`: ONE per device for the whole process, shared by every handle and never
@@ -1085,15 +1038,14 @@ int run(ghost_aei* h, Mode mode, int B, const Io& io, void* ws, int64_t ws_bytes
   dry.h = h; dry.dry = true;
   plan(dry, mode, B, io);
   if (!dry.ok()) return fail(dry.rc, dry.where);
-  const size_t main_bytes = ((dry.off + 255) & ~size_t(255)) + kMainSlack;
-  const size_t scr = (dry.scratch_need + 255) & ~size_t(255);
+  const size_t main_bytes = align_up(dry.off) + kMainSlack;
+  const size_t scr = align_up(dry.scratch_need);
   const size_t need = main_bytes + kSemBytes + (dry.dual ? 2 : 1) * scr + 256;
   if (!ws || (size_t)ws_bytes < need)
     return fail(GHOST_ENOWS, "workspace too small: need " + std::to_string(need) + " bytes");
   Ctx c{};
   c.h = h; c.dry = false;
-  c.base = (char*)(((uintptr_t)ws + 255) & ~uintptr_t(255));
-  c.cap = main_bytes;
+  c.base = align_up(ws);
   c.scratch = c.base + main_bytes + kSemBytes;
   c.scratch_cap = dry.scratch_need;
   c.s = (hipStream_t)stream;
@@ -1150,8 +1102,6 @@ extern "C" int ghost_aei_create(const char* backbone, int num_blocks, int c_id, 
 
 extern "C" void ghost_aei_destroy(ghost_aei* h) {
   if (!h) return;
-  for (auto e : h->ev) (void)hipEventDestroy(e);
-  if (h->clk) (void)hipFree(h->clk);
   for (auto& kv : h->up_path) {
     for (auto e : kv.second.zev)
       if (e) (void)hipEventDestroy(e);
@@ -1162,26 +1112,12 @@ extern "C" void ghost_aei_destroy(ghost_aei* h) {
 }
 
 extern "C" int ghost_aei_bind(ghost_aei* h, const char* name, const void* p, int64_t numel) {
-  if (!h || !name) return fail(GHOST_EINVAL, "null argument");
-  auto it = h->slots.find(name);
-  if (it == h->slots.end()) return fail(GHOST_EINVAL, std::string("unknown weight slot ") + name);
-  if (!p || numel <= 0) return fail(GHOST_EINVAL, std::string("null/empty tensor for slot ") + name);
-  if ((uintptr_t)p % 16) return fail(GHOST_EINVAL, std::string("slot not 16-byte aligned: ") + name);
-  it->second = p;
-  return 0;
+  return bind_slot(h ? &h->slots : nullptr, name, p, numel, "null/empty tensor for slot ", true);
 }
 
 extern "C" int ghost_aei_missing(ghost_aei* h) {
   if (!h) return fail(GHOST_EINVAL, "null handle");
-  int n = 0;
-  std::string first;
-  for (auto& kv : h->slots)
-    if (!kv.second) {
-      if (!n) first = kv.first;
-      ++n;
-    }
-  if (n) g_err = "unbound weight slot " + first;
-  return n;
+  return count_missing(h->slots);
 }
 
 extern "C" int ghost_aei_attr_geometry(ghost_aei* h, int level, int* C, int* H, int* W) {
@@ -1271,7 +1207,8 @@ extern "C" int ghost_aei_swap_u8_indexed(ghost_aei* h, const uint8_t* crops, int
                                          const int32_t* identity_index, uint8_t* out_u8, void* ws, int64_t ws_bytes,
                                          void* stream) {
   if (!crops || !table || !identity_index || !out_u8) return fail(GHOST_EINVAL, "null argument");
-  if (!h || n_ident <= 0) return fail(GHOST_EINVAL, "n_ident must be positive");
+  if (!h) return fail(GHOST_EINVAL, "null handle");
+  if (n_ident <= 0) return fail(GHOST_EINVAL, "n_ident must be positive");
   if ((uintptr_t)table % 256) return fail(GHOST_EINVAL, "identity table must be 256-byte aligned");
   // the clamped gather reads rows [0, n_ident) only: a table of fewer rows is refused here, not read past its end
   if (table_bytes_ < (int64_t)table_bytes(h, n_ident)) return fail(GHOST_EINVAL, "identity table too small for n_ident");
@@ -1291,85 +1228,31 @@ extern "C" int ghost_aei_up_stream(ghost_aei* h, int device, void** stream) {
 
 extern "C" int ghost_aei_profile(ghost_aei* h, int class_mask) {
   if (!h) return fail(GHOST_EINVAL, "null handle");
-  h->prof_mask = class_mask;
-  h->pend.clear();
-  h->ev_used = 0;
-  for (auto& p : h->prof) p = ProfClass{};
-  h->clk_used = 0;
-  h->clk_launch.clear();
-  if (class_mask & 2) {   // class 1: arm the in-kernel clock (buffer on the current device)
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(GHOST_EINVAL, "hipGetDevice failed");
-    if (h->clk && h->clk_dev != dev) {
-      (void)hipFree(h->clk);
-      h->clk = nullptr;
-    }
-    if (!h->clk) {
-      h->clk_cap = size_t(8) << 20;   // 64 MB: 227 launches of the B = 64 256x256 kernel
-      if (hipMalloc(&h->clk, sizeof(unsigned long long) * h->clk_cap) != hipSuccess) {
-        h->clk = nullptr;
-        return fail(GHOST_EINVAL, "clock buffer allocation failed");
-      }
-      h->clk_dev = dev;
-    }
-  }
-  return 0;
+  const char* err = h->prof.reset(class_mask);
+  return err ? fail(GHOST_EINVAL, err) : 0;
 }
 
 extern "C" int ghost_aei_profile_clock(ghost_aei* h, double* us_total, int64_t* launches, int* kernel_version) {
   if (!h || !us_total || !launches) return fail(GHOST_EINVAL, "null argument");
   *us_total = 0;
   *launches = 0;
-  if (kernel_version) *kernel_version = h->roof_version;
-  if (!h->clk || h->clk_launch.empty()) return 0;
-  std::vector<unsigned long long> v(h->clk_used);
-  if (hipMemcpy(v.data(), h->clk, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(GHOST_EINVAL, "clock buffer read failed");
-  int rate_khz = 0;
-  if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, h->clk_dev) != hipSuccess || rate_khz <= 0)
-    return fail(GHOST_EINVAL, "wall clock rate unavailable");
-  double ticks = 0;
-  int64_t n = 0;
-  for (auto& L : h->clk_launch) {
-    const size_t grid = (size_t)L.second / 9;   // 1 start + 8 wave ends per workgroup
-    unsigned long long t0 = ~0ull, t1 = 0;
-    for (size_t i = 0; i < grid; ++i) t0 = std::min(t0, v[L.first + i]);
-    for (size_t i = grid; i < (size_t)L.second; ++i) t1 = std::max(t1, v[L.first + i]);
-    if (t1 <= t0) continue;
-    ticks += (double)(t1 - t0);
-    ++n;
-  }
-  *us_total = ticks / (rate_khz * 1e-3);
-  *launches = n;
-  return 0;
+  if (kernel_version) *kernel_version = h->prof.roof_version;
+  const char* err = h->prof.read_clock(us_total, launches);
+  return err ? fail(GHOST_EINVAL, err) : 0;
 }
 
 extern "C" int ghost_aei_profile_read(ghost_aei* h, int cls, double* ms, int64_t* launches, double* bytes,
                                       double* flops) {
-  if (!h || cls < 0 || cls >= 8) return fail(GHOST_EINVAL, "bad argument");
-  // fold completed brackets into the class totals (caller synchronised the stream)
-  for (auto& p : h->pend) {
-    float t = 0.f;
-    hipError_t e = hipEventElapsedTime(&t, h->ev[p.e0], h->ev[p.e1]);
-    if (e != hipSuccess) return fail((int)e, "hipEventElapsedTime failed (stream not synchronised?)");
-    ProfClass& pc = h->prof[p.cls];
-    pc.ms += t;
-    pc.launches += 1;
-    pc.bytes += p.bytes;
-    pc.flops += p.flops;
-  }
-  h->pend.clear();
-  h->ev_used = 0;
-  if (ms) *ms = h->prof[cls].ms;
-  if (launches) *launches = h->prof[cls].launches;
-  if (bytes) *bytes = h->prof[cls].bytes;
-  if (flops) *flops = h->prof[cls].flops;
+  if (!h || cls < 0 || cls >= PROF_NCLS) return fail(GHOST_EINVAL, "bad argument");
+  if (int e = h->prof.fold()) return fail(e, "hipEventElapsedTime failed (stream not synchronised?)");
+  const Profiler::Total& t = h->prof.total[cls];
+  if (ms) *ms = t.ms;
+  if (launches) *launches = t.launches;
+  if (bytes) *bytes = t.bytes;
+  if (flops) *flops = t.flops;
   return 0;
 }
 
-// ---------------------------------------------------------------------------
-// C ABI: single operators
-// ---------------------------------------------------------------------------
 extern "C" int ghost_aei_set_option(ghost_aei* h, int option, int value) {
   if (!h) return fail(GHOST_EINVAL, "null handle");
   if (option < 0 || option >= GHOST_AEI_NOPT) return fail(GHOST_EINVAL, "unknown option");
@@ -1390,312 +1273,4 @@ extern "C" int ghost_aei_set_taps(ghost_aei* h, void* const taps[8]) {
   if (!h) return fail(GHOST_EINVAL, "null handle");
   for (int k = 0; k < 8; ++k) h->taps[k] = taps ? taps[k] : nullptr;
   return 0;
-}
-
-static int conv_op(ConvDesc& d, void* ws, int64_t ws_bytes, void* stream, const char* what) {
-  const size_t need = conv_workspace_bytes(d);
-  if (need > 0 && (!ws || (size_t)ws_bytes < need))
-    return fail(GHOST_ENOWS, std::string(what) + ": workspace too small, need " + std::to_string(need));
-  int rc = conv_launch(d, ws, (size_t)ws_bytes, (hipStream_t)stream);
-  if (rc) return fail(rc, std::string(what) + " failed");
-  return 0;
-}
-
-extern "C" int ghost_conv2d_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx, const void* w_packed,
-                                 int Cout, int Npad, int Kpad, int kh, int kw, int stride, int pad, const float* scale,
-                                 const float* shift, float slope, const void* res, int ldres, int tanh_out, void* y,
-                                 int ldy, void* ws, int64_t ws_bytes, void* stream) {
-  ConvDesc d;
-  d.ti = d.to = dtype;
-  d.x = x; d.B = B; d.Hi = H; d.Wi = W; d.Cin = Cin; d.ldx = ldx;
-  d.w = w_packed; d.N = Cout; d.Npad = Npad; d.Kpad = Kpad;
-  d.kind = CONV_FWD; d.kh = kh; d.kw = kw; d.stride = stride; d.pad = pad;
-  d.scale = scale; d.shift = shift; d.slope = slope; d.res = res; d.ldres = ldres; d.tanh_out = tanh_out;
-  d.y = y; d.ldy = ldy;
-  return conv_op(d, ws, ws_bytes, stream, "ghost_conv2d_nhwc");
-}
-
-extern "C" int ghost_conv2d_ex_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx,
-                                    const void* w_packed, int Cout, int Npad, int Kpad, int kh, int kw, int stride,
-                                    int pad, const ghost_conv_epi* epi, void* y, int ldy, void* ws, int64_t ws_bytes,
-                                    void* stream) {
-  if (!epi) return fail(GHOST_EINVAL, "ghost_conv2d_ex_nhwc: null epilogue");
-  ConvDesc d;
-  d.ti = d.to = dtype;
-  d.x = x; d.B = B; d.Hi = H; d.Wi = W; d.Cin = Cin; d.ldx = ldx;
-  d.w = w_packed; d.N = Cout; d.Npad = Npad; d.Kpad = Kpad;
-  d.kind = CONV_FWD; d.kh = kh; d.kw = kw; d.stride = stride; d.pad = pad;
-  d.scale = epi->scale; d.shift = epi->shift; d.slope = epi->slope; d.prelu = epi->prelu;
-  d.res = epi->res; d.ldres = epi->ldres; d.res_first = epi->res_first; d.tanh_out = epi->tanh_out;
-  d.y2 = epi->y2; d.ldy2 = epi->ldy2; d.scale2 = epi->scale2; d.shift2 = epi->shift2;
-  if (epi->split_k < 0) return fail(GHOST_EINVAL, "ghost_conv2d_ex_nhwc: split_k must be >= 0");
-  d.force_split = epi->split_k;
-  d.y = y; d.ldy = ldy;
-  return conv_op(d, ws, ws_bytes, stream, "ghost_conv2d_ex_nhwc");
-}
-
-extern "C" int ghost_conv_transpose4x4s2_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx,
-                                              const void* w_packed, int Cout, int Npad, int Kpad, const float* scale,
-                                              const float* shift, float slope, const void* res, int ldres, void* y,
-                                              int ldy, void* ws, int64_t ws_bytes, void* stream) {
-  ConvDesc d;
-  d.ti = d.to = dtype;
-  d.x = x; d.B = B; d.Hi = H; d.Wi = W; d.Cin = Cin; d.ldx = ldx;
-  d.w = w_packed; d.N = Cout; d.Npad = Npad; d.Kpad = Kpad;
-  d.kind = CONV_T4S2;
-  d.scale = scale; d.shift = shift; d.slope = slope; d.res = res; d.ldres = ldres;
-  d.y = y; d.ldy = ldy;
-  return conv_op(d, ws, ws_bytes, stream, "ghost_conv_transpose4x4s2_nhwc");
-}
-
-extern "C" int ghost_linear_f32(const float* x, int B, int K, const float* w_packed, int N, int Npad, int Kpad,
-                                const float* bias, int out_dtype, void* y, int ldy, void* ws, int64_t ws_bytes,
-                                void* stream) {
-  ConvDesc d;
-  d.ti = GHOST_F32; d.to = out_dtype;
-  d.x = x; d.B = B; d.Hi = 1; d.Wi = 1; d.Cin = K; d.ldx = K;
-  d.w = w_packed; d.N = N; d.Npad = Npad; d.Kpad = Kpad;
-  d.shift = bias; d.y = y; d.ldy = ldy;
-  return conv_op(d, ws, ws_bytes, stream, "ghost_linear_f32");
-}
-
-extern "C" int ghost_instnorm_stats_nhwc(int dtype, const void* x, int B, int HW, int C, int ldx, float* stat, void* ws,
-                                         int64_t ws_bytes, void* stream) {
-  if ((size_t)ws_bytes < in_stats_workspace_bytes(B, HW, C)) return fail(GHOST_ENOWS, "in_stats: workspace too small");
-  int rc = in_stats(dtype, x, ldx, B, HW, C, stat, ws, (size_t)ws_bytes, (hipStream_t)stream);
-  return rc ? fail(rc, "in_stats failed") : 0;
-}
-
-extern "C" int ghost_instnorm_stats_up2x_nhwc(int dtype, const void* x, int B, int H, int W, int C, int ldx,
-                                              float* stat, void* ws, int64_t ws_bytes, void* stream) {
-  if ((size_t)ws_bytes < in_stats_workspace_bytes(B, 4 * H * W, C))
-    return fail(GHOST_ENOWS, "in_stats_up2x: workspace too small");
-  int rc = in_stats_up2x(dtype, x, ldx, B, H, W, C, stat, ws, (size_t)ws_bytes, (hipStream_t)stream);
-  return rc ? fail(rc, "in_stats_up2x failed") : 0;
-}
-
-extern "C" int ghost_aad_layer_nhwc(int dtype, const void* h_in, int ldh, const void* z_attr, int lda, int B, int H,
-                                    int W, int C, int Ca, const void* gbw_packed, int Npad, int Kpad, const float* gbb,
-                                    const float* wh, const float* bh, const float* idgb, int id_ld, float slope,
-                                    void* out, int ldo, void* ws, int64_t ws_bytes, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int HW = H * W;
-  // workspace: stat [B][C][2] | mask [B*HW] | scratch (max of IN partials and split-K partials)
-  const size_t stat_b = ((size_t)B * C * 2 * sizeof(float) + 255) & ~size_t(255);
-  const size_t mask_b = ((size_t)B * HW * sizeof(float) + 255) & ~size_t(255);
-  ConvDesc d;
-  d.ti = d.to = dtype;
-  d.x = z_attr; d.B = B; d.Hi = H; d.Wi = W; d.Cin = Ca; d.ldx = lda;
-  d.w = gbw_packed; d.N = 2 * C; d.Npad = Npad; d.Kpad = Kpad;
-  d.kind = CONV_FWD; d.kh = d.kw = 1;
-  d.y = out; d.ldy = ldo; d.shift = gbb; d.slope = slope; d.epi = EPI_AAD;
-  d.hin = h_in; d.ldh = ldh; d.idgb = idgb; d.id_ld = id_ld; d.C_aad = C;
-  size_t sc = conv_workspace_bytes(d);
-  const size_t st = in_stats_workspace_bytes(B, HW, C);
-  if (st > sc) sc = st;
-  char* base = (char*)(((uintptr_t)ws + 255) & ~uintptr_t(255));
-  if (!ws || (size_t)ws_bytes < stat_b + mask_b + sc + 256) return fail(GHOST_ENOWS, "aad_layer: workspace too small");
-  float* stat = (float*)base;
-  float* mask = (float*)(base + stat_b);
-  char* scratch = base + stat_b + mask_b;
-  int rc = in_stats(dtype, h_in, ldh, B, HW, C, stat, scratch, sc, s);
-  if (rc) return fail(rc, "aad_layer: in_stats failed");
-  // this entry takes gbw, not the w3 / b3 layout: Fused or Split
-  if (aad_path(dtype, B, HW, C, Ca, lda, ldh, &ldo, 1, false) == AadPath::Fused) {
-    rc = aad_fused(dtype, z_attr, lda, Ca, gbw_packed, Kpad, gbb, h_in, ldh, stat, wh, bh, idgb, id_ld, out, ldo, B, HW, C,
-                   slope, s);
-    return rc ? fail(rc, "aad_layer: fused kernel failed") : 0;
-  }
-  rc = aad_mask(dtype, h_in, ldh, B, HW, C, stat, wh, bh, mask, s);
-  if (rc) return fail(rc, "aad_layer: mask failed");
-  d.stat = stat; d.mask = mask;
-  rc = conv_launch(d, scratch, sc, s);
-  if (rc) return fail(rc, "aad_layer: gemm failed");
-  return 0;
-}
-
-extern "C" int ghost_upsample2x_nhwc(int dtype, const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C,
-                                     void* stream) {
-  int rc = upsample2x(dtype, x, ldx, y, ldy, B, H, W, C, (hipStream_t)stream);
-  return rc ? fail(rc, "upsample2x failed") : 0;
-}
-
-extern "C" int ghost_nhwc_to_nchw(int dtype, const void* x, int ldx, int B, int H, int W, int C, void* y, void* stream) {
-  int rc = nhwc_to_nchw(dtype, x, ldx, B, H, W, C, y, (hipStream_t)stream);
-  return rc ? fail(rc, "nhwc_to_nchw failed") : 0;
-}
-
-extern "C" int ghost_crops_to_input_nhwc(const uint8_t* crops, int64_t crop_batch_stride, int B, int H, int W, int dtype,
-                                         void* y, void* stream) {
-  int rc = crops_u8_to_input(crops, crop_batch_stride, B, H, W, dtype, y, (hipStream_t)stream, 3);
-  return rc ? fail(rc, "crops_to_input failed") : 0;
-}
-
-extern "C" int ghost_conv3x3_narrow_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx,
-                                         const void* w_narrow, int Kpad, int Cout, const void* res, int ldres,
-                                         int tanh_out, void* y, int ldy, uint8_t* u8, void* stream) {
-  int rc = conv3x3_narrow(dtype, x, B, H, W, Cin, ldx, w_narrow, Kpad, Cout, res, ldres, tanh_out, y, ldy, u8,
-                          (hipStream_t)stream);
-  return rc ? fail(rc, "conv3x3_narrow failed (H % 8, W % 32, Cin % 32 and Cout <= 3 required)") : 0;
-}
-
-extern "C" int ghost_aad_layers_v3_dt_nhwc(int dtype, const void* h_in, int ldh, int up2x, const void* z_attr, int lda,
-                                           int B, int H, int W, int C, int Ca, int L, const void* const w3[],
-                                           const float* const b3[], const float* const wh[], const float* const bh[],
-                                           const float* const idgb[], int id_ld, float slope, void* const out[],
-                                           const int ldo[], void* ws, int64_t ws_bytes, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int HW = H * W;
-  if (L < 1 || L > 2) return fail(GHOST_EINVAL, "aad_v3: L must be 1 or 2");
-  if (up2x & ~1) return fail(GHOST_EINVAL, "aad_v3: up2x must be 0 or 1");
-  if (up2x && (H % 2 || W % 2 || (C != 64 && C != 128)))
-    return fail(GHOST_EINVAL, "aad_v3: up2x needs even H, W and C in {64, 128}");
-  // aad_wide: one layer, C in {256, 512, 1024}, Ca <= 512, where the all-channel kernel does not fit
-  const AadPath path = aad_path(dtype, B, HW, C, Ca, lda, ldh, ldo, L);
-  const bool wide = path == AadPath::Wide;
-  if (wide ? (L != 1 || up2x) : path != AadPath::V3)
-    return fail(GHOST_EINVAL, "aad_v3 / aad_wide: unsupported shape (bf16 / fp16, a planner's (C, Ca), enough pixels; "
-                              "aad_wide: one layer, no upsample)");
-  const size_t stat_b = ((size_t)B * C * 2 * sizeof(float) + 255) & ~size_t(255);
-  const size_t sc = in_stats_workspace_bytes(B, HW, C);
-  char* base = (char*)(((uintptr_t)ws + 255) & ~uintptr_t(255));
-  if (!ws || (size_t)ws_bytes < stat_b + sc + 256) return fail(GHOST_ENOWS, "aad_v3: workspace too small");
-  float* stat = (float*)base;
-  int rc = up2x ? in_stats_up2x(dtype, h_in, ldh, B, H / 2, W / 2, C, stat, base + stat_b, sc, s)
-                : in_stats(dtype, h_in, ldh, B, HW, C, stat, base + stat_b, sc, s);
-  if (rc) return fail(rc, "aad_v3: in_stats failed");
-  if (wide) {
-    const size_t mask_b = ((size_t)B * HW * sizeof(float) + 255) & ~size_t(255);
-    if ((size_t)ws_bytes < stat_b + sc + mask_b + 256) return fail(GHOST_ENOWS, "aad_wide: workspace too small");
-    float* mask = (float*)(base + stat_b + sc);
-    rc = aad_mask(dtype, h_in, ldh, B, HW, C, stat, wh[0], bh[0], mask, s);
-    if (rc) return fail(rc, "aad_wide: aad_mask failed");
-    AadWideDesc w;
-    w.dt = dtype;
-    w.mask = mask;
-    w.za = z_attr; w.lda = lda; w.Ca = Ca; w.hin = h_in; w.ldh = ldh; w.stat = stat;
-    w.B = B; w.HW = HW; w.C = C; w.id_ld = id_ld; w.slope = slope;
-    w.w3 = w3[0]; w.b3 = b3[0]; w.wh = wh[0]; w.bh = bh[0]; w.idgb = idgb[0]; w.out = out[0]; w.ldo = ldo[0];
-    rc = aad_wide(w, s);
-    return rc ? fail(rc, "aad_wide launch failed") : 0;
-  }
-  AadV3Desc d;
-  d.dt = dtype;
-  d.za = z_attr; d.lda = lda; d.Ca = Ca; d.hin = h_in; d.ldh = ldh; d.stat = stat;
-  d.B = B; d.HW = HW; d.C = C; d.L = L; d.id_ld = id_ld; d.slope = slope;
-  if (up2x) {
-    d.up_H = H / 2;
-    d.up_W = W / 2;
-  }
-  for (int l = 0; l < L; ++l) {
-    d.w3[l] = w3[l]; d.b3[l] = b3[l]; d.wh[l] = wh[l]; d.bh[l] = bh[l]; d.idgb[l] = idgb[l];
-    d.out[l] = out[l]; d.ldo[l] = ldo[l];
-  }
-  rc = aad_v3(d, s);
-  return rc ? fail(rc, "aad_v3 launch failed") : 0;
-}
-
-extern "C" int ghost_aad_layers_v3_nhwc(const void* h_in, int ldh, int up2x, const void* z_attr, int lda, int B, int H,
-                                        int W, int C, int Ca, int L, const void* const w3[], const float* const b3[],
-                                        const float* const wh[], const float* const bh[], const float* const idgb[],
-                                        int id_ld, float slope, void* const out[], const int ldo[], void* ws,
-                                        int64_t ws_bytes, void* stream) {
-  return ghost_aad_layers_v3_dt_nhwc(GHOST_BF16, h_in, ldh, up2x, z_attr, lda, B, H, W, C, Ca, L, w3, b3, wh, bh, idgb,
-                                     id_ld, slope, out, ldo, ws, ws_bytes, stream);
-}
-
-extern "C" int64_t ghost_aad_plan(int dtype, int B, int H, int W, int C, int Ca, int L, int up2x, int zp_mask,
-                                  float slope, int lda, int ldh, const int ldo[], char* buf, int64_t cap) {
-  if (L < 1 || L > 2 || !ldo || (up2x & ~1) || (zp_mask & ~3) || cap < 0 || (cap > 0 && !buf))
-    return fail(GHOST_EINVAL, "aad_plan: bad argument");
-  const int HW = H * W;
-  PlanSig sig;
-  sig.s[0] = 0;
-  const AadPath path = aad_path(dtype, B, HW, C, Ca, lda, ldh, ldo, L);
-  if (path == AadPath::V3) {
-    AadV3Desc d;
-    d.dt = dtype; d.B = B; d.HW = HW; d.C = C; d.Ca = Ca; d.L = L; d.lda = lda; d.ldh = ldh; d.slope = slope;
-    if (up2x) { d.up_H = H / 2; d.up_W = W / 2; }
-    for (int l = 0; l < L; ++l) {
-      d.ldo[l] = ldo[l];
-      if (zp_mask >> l & 1) d.zw[l] = &sig;   // the planner asks only whether it is set
-    }
-    d.zwld = 2 * C;   // the narrow conv layout's row of both K halves
-    const AadV3Plan p = aad_v3_plan(d);
-    if (p.kernel != AadV3Kernel::None) sig = aad_v3_signature(p, d);
-  } else if (path == AadPath::Wide && !up2x && !zp_mask) {
-    AadWideDesc d;
-    d.dt = dtype; d.B = B; d.HW = HW; d.C = C; d.Ca = Ca; d.lda = lda; d.ldh = ldh; d.ldo = ldo[0]; d.slope = slope;
-    const AadWidePlan p = aad_wide_plan(d, true);
-    if (p.kernel != AadWideKernel::None) sig = aad_wide_signature(p, d);
-  }
-  if (!sig.s[0]) return fail(GHOST_EINVAL, "aad_plan: no aad_v3 / aad_wide kernel takes this shape");
-  if (cap > 0) snprintf(buf, (size_t)cap, "%s", sig.s);
-  return (int64_t)strlen(sig.s) + 1;
-}
-
-extern "C" int64_t ghost_conv_plan(int ti, int to, int kind, int B, int H, int W, int Cin, int ldx, int N, int Npad,
-                                   int Kpad, int kh, int kw, int stride, int pad, int ldy, int epi, int split_k,
-                                   int min_wgs, int nsem, int ncu, int flags, int64_t* ws_bytes, char* buf, int64_t cap) {
-  if ((kind != CONV_FWD && kind != CONV_T4S2) || (epi != EPI_STD && epi != EPI_AAD) || split_k < 0 || nsem < 0 ||
-      ncu < 1 || (flags & ~GHOST_CONV_PLAN_FLAGS) || cap < 0 || (cap > 0 && !buf))
-    return fail(GHOST_EINVAL, "conv_plan: bad argument");
-  alignas(16) static char mem[16];   // stands for every pointer: the planners ask only whether one is set and aligned
-  float* const fp = reinterpret_cast<float*>(mem);
-  ConvDesc d;
-  d.ti = ti; d.to = to; d.kind = kind;
-  d.x = mem; d.B = B; d.Hi = H; d.Wi = W; d.Cin = Cin; d.ldx = ldx;
-  d.w = mem; d.N = N; d.Npad = Npad; d.Kpad = Kpad;
-  d.kh = kh; d.kw = kw; d.stride = stride; d.pad = pad;
-  d.y = mem; d.ldy = ldy; d.scale = fp; d.shift = fp;
-  d.epi = epi; d.force_split = split_k; d.min_wgs = min_wgs;
-  if (nsem) { d.sem = reinterpret_cast<unsigned*>(mem); d.nsem = nsem; }
-  if (epi == EPI_AAD) { d.C_aad = N / 2; d.hin = mem; d.ldh = N / 2; d.stat = d.idgb = d.mask = fp; d.id_ld = N; }
-  if (flags & GHOST_CONV_PLAN_RES) { d.res = mem; d.ldres = ldy; }
-  d.res_first = (flags & GHOST_CONV_PLAN_RES_FIRST) != 0;
-  if (flags & GHOST_CONV_PLAN_PRELU) d.prelu = fp;
-  if (flags & GHOST_CONV_PLAN_Y2) { d.y2 = mem; d.ldy2 = ldy; d.scale2 = d.shift2 = fp; }
-  if (flags & GHOST_CONV_PLAN_U8) d.u8 = reinterpret_cast<uint8_t*>(mem);
-  d.tanh_out = (flags & GHOST_CONV_PLAN_TANH) != 0;
-  if (flags & GHOST_CONV_PLAN_IN_PART) d.in_part = fp;
-  if (!conv_desc_ok(d)) return fail(GHOST_EINVAL, "conv_plan: conv_launch rejects this descriptor");
-  std::string text;
-  switch (conv_path(d)) {
-    case ConvPath::Halo3x3: {
-      const HaloPlan p = halo_plan(d, ncu);
-      if (d.in_part && !p.stats) return fail(GHOST_EINVAL, "conv_plan: this halo plan writes no InstanceNorm partials");
-      text = halo_signature(p, d).s;
-      break;
-    }
-    case ConvPath::First: text = conv_first_signature(d).s; break;
-    case ConvPath::Stem3x3: text = conv_stem3x3_signature(d).s; break;
-    case ConvPath::ConvTHalo: text = convT_halo_signature(d).s; break;
-    case ConvPath::S2Patch: text = conv_s2_patch_signature(d).s; break;
-    case ConvPath::Igemm: {
-      const IgemmPlan p = igemm_plan(d);
-      if (p.kernel == IgemmKernel::None) return fail(GHOST_EINVAL, "conv_plan: no implicit-GEMM instance takes this descriptor");
-      text = igemm_signature(p, d).s;
-      if (p.reduce != IgemmReduce::None) text += std::string("\n") + igemm_reduce_signature(p, d).s;
-      break;
-    }
-  }
-  if (ws_bytes) *ws_bytes = (int64_t)conv_workspace_bytes(d);
-  if (cap > 0) snprintf(buf, (size_t)cap, "%s", text.c_str());
-  return (int64_t)text.size() + 1;
-}
-
-extern "C" int ghost_aad_mask_nhwc(int dtype, const void* h, int ldh, int B, int HW, int C, float* stat, const float* wh0,
-                                   const float* bh0, float* mask0, const float* wh1, const float* bh1, float* mask1,
-                                   int small, void* stream) {
-  if (!h || !stat || !wh0 || !bh0 || !mask0 || (wh1 && (!bh1 || !mask1)))
-    return fail(GHOST_EINVAL, "aad_mask: null argument");
-  if (B < 1 || HW < 1 || C < 1) return fail(GHOST_EINVAL, "aad_mask: empty shape");
-  if (small) {
-    if (!stats_mask_small_ok(dtype, HW, C, ldh))
-      return fail(GHOST_EINVAL, "aad_mask: small form needs HW <= 16, C <= 1024, C and ldh multiples of the vector");
-    int rc = stats_mask_small(dtype, h, ldh, B, HW, C, stat, wh0, bh0, mask0, wh1, bh1, mask1, (hipStream_t)stream);
-    return rc ? fail(rc, "stats_mask_small failed") : 0;
-  }
-  int rc = aad_mask2(dtype, h, ldh, B, HW, C, stat, wh0, bh0, mask0, wh1, bh1, mask1, (hipStream_t)stream);
-  return rc ? fail(rc, "aad_mask2 failed") : 0;
 }

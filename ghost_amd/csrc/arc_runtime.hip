@@ -25,19 +25,17 @@
 #include "ghost_common.h"
 #include "conv_igemm.h"
 #include "ops.h"
+#include "plan_ctx.h"
 
 using namespace ghost;
 
-namespace ghost {
-int set_last_error(int rc, const std::string& msg);   // aei_runtime.hip (ghost_last_error)
-}
 static int arc_fail(int rc, const std::string& msg) { return ghost::set_last_error(rc, msg); }
 
 struct ghost_arc {
   int layers[4] = {3, 13, 30, 3};
   int nf = 512;
   int dt = GHOST_F32, esz = 4;
-  std::map<std::string, const void*> slots;
+  Slots slots;
   // diagnostic taps (ghost_arc_set_taps): stage i (0 = stem, i = block i) copies its stored residual
   // stream X into taps[2i] and the next BatchNorm's second output XB into taps[2i+1] when non-null
   std::vector<void*> taps;
@@ -46,43 +44,9 @@ struct ghost_arc {
 namespace {
 
 const int kWidths[4] = {64, 128, 256, 512};
-inline int rup(int v, int m) { return (v + m - 1) / m * m; }
-
-struct ArcCtx {
-  ghost_arc* h;
-  bool dry;
-  char* base = nullptr;
-  size_t off = 0;
-  size_t scratch_need = 0;
-  char* scratch = nullptr;
-  size_t scratch_cap = 0;
-  hipStream_t s = nullptr;
-  int rc = 0;
-  std::string where;
-
-  void* alloc(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    void* p = dry ? reinterpret_cast<void*>(uintptr_t(0x10000000) + off) : base + off;
-    off += bytes;
-    return p;
-  }
-  bool ok() const { return rc == 0; }
-  void check(int r, const std::string& what) {
-    if (r != 0 && rc == 0) { rc = r; where = what; }
-  }
-  const void* W(const std::string& name) {
-    auto it = h->slots.find(name);
-    if (it == h->slots.end()) {
-      if (rc == 0) { rc = GHOST_EINVAL; where = "plan reads undeclared slot " + name; }
-      return nullptr;
-    }
-    if (dry) return reinterpret_cast<const void*>(uintptr_t(0x1000));
-    if (!it->second) {
-      if (rc == 0) { rc = GHOST_ENOTREADY; where = "unbound weight slot " + name; }
-      return nullptr;
-    }
-    return it->second;
-  }
+struct ArcCtx : PlanCtx {
+  ghost_arc* h = nullptr;
+  const void* W(const std::string& name) { return PlanCtx::W(h->slots, name); }
 };
 
 static int arc_min_wgs() {
@@ -93,11 +57,7 @@ static int arc_min_wgs() {
 void run_conv(ArcCtx& c, ConvDesc& d, const std::string& what) {
   if (!c.ok()) return;
   d.min_wgs = arc_min_wgs();
-  if (c.dry) {
-    const size_t need = conv_workspace_bytes(d);
-    if (need > c.scratch_need) c.scratch_need = need;
-    return;
-  }
+  if (c.dry) return c.need_scratch(conv_workspace_bytes(d));
   c.check(conv_launch(d, c.scratch, c.scratch_cap, c.s), what);
 }
 
@@ -106,13 +66,7 @@ void conv_bn(ArcCtx& c, const std::string& w, const std::string& bn, const void*
              int Cout, int k, int stride, void* y, const char* prelu, const void* res, void* y2,
              const std::string& bn2name) {
   ghost_arc* h = c.h;
-  ConvDesc d;
-  d.ti = d.to = h->dt;
-  d.x = x; d.B = N; d.Hi = H; d.Wi = H; d.Cin = Cin; d.ldx = ldx;
-  d.w = c.W(w);
-  d.N = Cout; d.Npad = rup(Cout, 128); d.Kpad = rup(k * k * Cin, 32);
-  d.kind = CONV_FWD; d.kh = d.kw = k; d.stride = stride; d.pad = k / 2;
-  d.y = y; d.ldy = Cout;
+  ConvDesc d = conv_desc(h->dt, h->dt, x, N, H, Cin, ldx, c.W(w), Cout, CONV_FWD, k, stride, k / 2, y, Cout);
   d.scale = (const float*)c.W(bn + ".scale");
   d.shift = (const float*)c.W(bn + ".shift");
   d.slope = 1.f;
@@ -177,13 +131,7 @@ void arc_plan(ArcCtx& c, const void* xin, int N, float* emb) {
     tap(i + 1, X[cur], XB[cur], (size_t)N * H * H * C * es);
   }
   // head: fc over flatten(bn2(X)) as a 7x7 valid conv, features BatchNorm1d folded with the fc bias
-  ConvDesc d;
-  d.ti = h->dt; d.to = GHOST_F32;
-  d.x = XB[cur]; d.B = N; d.Hi = H; d.Wi = H; d.Cin = C; d.ldx = C;
-  d.w = c.W("fc.w");
-  d.N = h->nf; d.Npad = rup(h->nf, 128); d.Kpad = rup(H * H * C, 32);
-  d.kind = CONV_FWD; d.kh = d.kw = H; d.stride = 1; d.pad = 0;
-  d.y = emb; d.ldy = h->nf;
+  ConvDesc d = conv_desc(h->dt, GHOST_F32, XB[cur], N, H, C, C, c.W("fc.w"), h->nf, CONV_FWD, H, 1, 0, emb, h->nf);
   d.scale = (const float*)c.W("fc.scale");
   d.shift = (const float*)c.W("fc.shift");
   d.slope = 1.f;
@@ -215,7 +163,7 @@ int64_t arc_bytes(ghost_arc* h, int N, size_t* scratch) {
   if (!c.ok()) return c.rc;
   c.alloc(256);   // u8 max flag
   *scratch = c.scratch_need;
-  return (int64_t)(((c.off + 255) & ~size_t(255)) + c.scratch_need + 256);
+  return (int64_t)(align_up(c.off) + c.scratch_need + 256);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -341,15 +289,14 @@ int run_arc(ghost_arc* h, int N, const void* xt, int xt_dtype, const int64_t* st
             int64_t crop_bs, int Hs, int Ws, float* emb, void* ws, int64_t ws_bytes, void* stream) {
   if (!h) return arc_fail(GHOST_EINVAL, "null handle");
   if (N <= 0 || N > 65535) return arc_fail(GHOST_EINVAL, "batch must be in 1..65535");
-  for (auto& kv : h->slots)
-    if (!kv.second) return arc_fail(GHOST_ENOTREADY, "unbound weight slot " + kv.first);
+  if (count_missing(h->slots)) return GHOST_ENOTREADY;
   size_t scratch = 0;
   const int64_t need = arc_bytes(h, N, &scratch);
   if (need < 0) return arc_fail((int)need, "plan sizing failed");
   if (!ws || ws_bytes < need) return arc_fail(GHOST_ENOWS, "workspace too small: need " + std::to_string(need));
   ArcCtx c{};
   c.h = h; c.dry = false;
-  c.base = (char*)(((uintptr_t)ws + 255) & ~uintptr_t(255));
+  c.base = align_up(ws);
   c.s = (hipStream_t)stream;
   void* xin = c.alloc((size_t)N * 112 * 112 * 4 * h->esz);
   // same allocation order as arc_bytes: the plan's buffers, then the flag, then the scratch
@@ -357,7 +304,7 @@ int run_arc(ghost_arc* h, int N, const void* xt, int xt_dtype, const int64_t* st
   probe.h = h; probe.dry = true;
   probe.alloc((size_t)N * 112 * 112 * 4 * h->esz);
   arc_plan(probe, probe.base, N, emb);
-  const size_t plan_end = (probe.off + 255) & ~size_t(255);
+  const size_t plan_end = align_up(probe.off);
   int* flag = (int*)(c.base + plan_end);
   c.scratch = c.base + plan_end + 256;
   c.scratch_cap = scratch;
@@ -409,23 +356,12 @@ extern "C" int ghost_arc_create(const int layers[4], int num_features, int dtype
 extern "C" void ghost_arc_destroy(ghost_arc* h) { delete h; }
 
 extern "C" int ghost_arc_bind(ghost_arc* h, const char* name, const void* p, int64_t numel) {
-  if (!h || !name) return arc_fail(GHOST_EINVAL, "null argument");
-  auto it = h->slots.find(name);
-  if (it == h->slots.end()) return arc_fail(GHOST_EINVAL, std::string("unknown weight slot ") + name);
-  if (!p || numel <= 0) return arc_fail(GHOST_EINVAL, std::string("empty tensor for ") + name);
-  it->second = p;
-  return 0;
+  return bind_slot(h ? &h->slots : nullptr, name, p, numel, "empty tensor for ", false);
 }
 
 extern "C" int ghost_arc_missing(ghost_arc* h) {
   if (!h) return arc_fail(GHOST_EINVAL, "null handle");
-  int n = 0;
-  for (auto& kv : h->slots)
-    if (!kv.second) {
-      if (n == 0) arc_fail(GHOST_ENOTREADY, "unbound weight slot " + kv.first);
-      ++n;
-    }
-  return n;
+  return count_missing(h->slots);
 }
 
 extern "C" int64_t ghost_arc_workspace_bytes(ghost_arc* h, int N) {

@@ -546,6 +546,7 @@ __global__ void __launch_bounds__(G::NW * 64) conv3x3_halo_pp_kernel(const HaloA
   // 389; one piece per tap or three measured no better.  (DBG & 4096: the old all-at-the-top issue, A/B only.)
   constexpr bool SPREAD = (DBG & 4096) == 0;
   constexpr int NPIECE = HPW + (RESW ? 0 : WPW);
+  static_assert(NPIECE <= 16, "the spread-issue switch below has sixteen cases");
   constexpr int PPT = 2;   // pieces per tap
   Tile cur = tile_of(0);
   set_dma_tile(cur);

@@ -68,6 +68,19 @@ struct ConvDesc {
   int nsem = 0;
 };
 
+// the shape of a descriptor; the caller adds what is particular to it (epilogue, residual, AAD fields).
+// CONV_T4S2 has its geometry built in: kh = kw = stride = 1 and pad = 0 there, as the struct's defaults
+inline ConvDesc conv_desc(int ti, int to, const void* x, int B, int Hi, int Wi, int Cin, int ldx, const void* w, int N,
+                          int Npad, int Kpad, int kind, int kh, int kw, int stride, int pad, void* y, int ldy) {
+  ConvDesc d;
+  d.ti = ti; d.to = to;
+  d.x = x; d.B = B; d.Hi = Hi; d.Wi = Wi; d.Cin = Cin; d.ldx = ldx;
+  d.w = w; d.N = N; d.Npad = Npad; d.Kpad = Kpad;
+  d.kind = kind; d.kh = kh; d.kw = kw; d.stride = stride; d.pad = pad;
+  d.y = y; d.ldy = ldy;
+  return d;
+}
+
 // ---- the implicit GEMM's plan: everything its launch needs, decided once from the descriptor ----
 struct ConvArgs;                                  // the kernels' argument block (conv_igemm.hip)
 typedef void (*ConvKernelFn)(const ConvArgs);

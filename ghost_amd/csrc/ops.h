@@ -10,8 +10,9 @@ namespace ghost {
 // 1/sqrt(biased var + eps) over H*W, from shifted partial sums (no Sigma x^2 - n mu^2
 // cancellation) merged in fp64.  stat = [B][C][2].
 size_t in_stats_workspace_bytes(int B, int HW, int C);
-// sem (optional, nsem >= B words, zero on entry and left zero): the partial kernel's last workgroup per sample
-// merges that sample's partials (one launch instead of two; same sums in the same order)
+// sem (optional, zero on entry and left zero): one counter per (sample, 64-channel group), nsem >= B * ceil(C/64)
+// words; the last of a counter's partial workgroups merges that group's partials (one launch instead of two; same
+// sums in the same order).  A sample that is a single chunk stores its statistics directly and counts nothing
 int in_stats(int dt, const void* x, int ldx, int B, int HW, int C, float* stat, void* ws, size_t ws_bytes,
              hipStream_t s, unsigned* sem = nullptr, int nsem = 0);
 // the same statistics of upsample2x(x) ([B, 2H, 2W, C], values rounded to dt) without materialising
