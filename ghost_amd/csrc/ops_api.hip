@@ -42,6 +42,13 @@ extern "C" int ghost_conv2d_nhwc(int dtype, const void* x, int B, int H, int W, 
   return conv_op(d, ws, ws_bytes, stream, "ghost_conv2d_nhwc");
 }
 
+static void set_epi(ConvDesc& d, const ghost_conv_epi* epi) {
+  d.scale = epi->scale; d.shift = epi->shift; d.slope = epi->slope; d.prelu = epi->prelu;
+  d.res = epi->res; d.ldres = epi->ldres; d.res_first = epi->res_first; d.tanh_out = epi->tanh_out;
+  d.y2 = epi->y2; d.ldy2 = epi->ldy2; d.scale2 = epi->scale2; d.shift2 = epi->shift2;
+  d.force_split = epi->split_k;
+}
+
 extern "C" int ghost_conv2d_ex_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx,
                                     const void* w_packed, int Cout, int Npad, int Kpad, int kh, int kw, int stride,
                                     int pad, const ghost_conv_epi* epi, void* y, int ldy, void* ws, int64_t ws_bytes,
@@ -49,12 +56,33 @@ extern "C" int ghost_conv2d_ex_nhwc(int dtype, const void* x, int B, int H, int 
   if (!epi) return fail(GHOST_EINVAL, "ghost_conv2d_ex_nhwc: null epilogue");
   ConvDesc d = conv_desc(dtype, dtype, x, B, H, W, Cin, ldx, w_packed, Cout, Npad, Kpad, CONV_FWD, kh, kw, stride, pad,
                          y, ldy);
-  d.scale = epi->scale; d.shift = epi->shift; d.slope = epi->slope; d.prelu = epi->prelu;
-  d.res = epi->res; d.ldres = epi->ldres; d.res_first = epi->res_first; d.tanh_out = epi->tanh_out;
-  d.y2 = epi->y2; d.ldy2 = epi->ldy2; d.scale2 = epi->scale2; d.shift2 = epi->shift2;
   if (epi->split_k < 0) return fail(GHOST_EINVAL, "ghost_conv2d_ex_nhwc: split_k must be >= 0");
-  d.force_split = epi->split_k;
+  set_epi(d, epi);
   return conv_op(d, ws, ws_bytes, stream, "ghost_conv2d_ex_nhwc");
+}
+
+// what aei_runtime.hip conv3x3() does with its stat argument: the conv writes per-(tile, wave) partials of its
+// output into the workspace, in_stats_from_tiles merges them
+extern "C" int ghost_conv2d_stats_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx,
+                                       const void* w_packed, int Cout, int Npad, int Kpad, int kh, int kw, int stride,
+                                       int pad, const ghost_conv_epi* epi, void* y, int ldy, float* stat, void* ws,
+                                       int64_t ws_bytes, void* stream) {
+  if (!epi || !stat) return fail(GHOST_EINVAL, "ghost_conv2d_stats_nhwc: null epilogue or stat");
+  if (epi->split_k < 0) return fail(GHOST_EINVAL, "ghost_conv2d_stats_nhwc: split_k must be >= 0");
+  ConvDesc d = conv_desc(dtype, dtype, x, B, H, W, Cin, ldx, w_packed, Cout, Npad, Kpad, CONV_FWD, kh, kw, stride, pad,
+                         y, ldy);
+  set_epi(d, epi);
+  int nrec = 0;
+  if (!conv_desc_ok(d) || conv_path(d) != ConvPath::Halo3x3 || !conv3x3_pp_takes(d, &nrec))
+    return fail(GHOST_EINVAL, "ghost_conv2d_stats_nhwc: the kernel of this conv writes no InstanceNorm partials");
+  const size_t need = (size_t)B * nrec * Cout * 2 * sizeof(float) + 256;
+  if (!ws || ws_bytes < 0 || (size_t)ws_bytes < need)
+    return fail(GHOST_ENOWS, "ghost_conv2d_stats_nhwc: workspace too small, need " + std::to_string(need));
+  d.in_part = (float*)align_up(ws);
+  int rc = conv_launch(d, nullptr, 0, (hipStream_t)stream);
+  if (rc) return fail(rc, "ghost_conv2d_stats_nhwc failed");
+  rc = in_stats_from_tiles(d.in_part, B, nrec, Cout, stat, (hipStream_t)stream);
+  return rc ? fail(rc, "ghost_conv2d_stats_nhwc: in_stats_from_tiles failed") : 0;
 }
 
 extern "C" int ghost_conv_transpose4x4s2_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx,

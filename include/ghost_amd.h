@@ -202,6 +202,15 @@ typedef struct ghost_conv_epi {
 int ghost_conv2d_ex_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx, const void* w_packed,
                          int Cout, int Npad, int Kpad, int kh, int kw, int stride, int pad, const ghost_conv_epi* epi,
                          void* y, int ldy, void* ws, int64_t ws_bytes, void* stream);
+/* ghost_conv2d_ex_nhwc whose kernel also writes the InstanceNorm partials of its output, merged into
+ * stat [B][Cout][2] (mean, rstd of the stored y per (sample, channel)) as the generator's 3x3 convs do it.  Only the
+ * persistent 3x3 kernels on exact 16 x 32 tiles or whole 8 x 8 images write partials: for any other descriptor
+ * GHOST_EINVAL, nothing launched.  Workspace: B * nrec * Cout * 2 floats + 256 bytes, nrec = H/16 * W/32 * 8 records
+ * per (sample, channel) (8 x 8 images: 1); GHOST_ENOWS names the need. */
+int ghost_conv2d_stats_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx, const void* w_packed,
+                            int Cout, int Npad, int Kpad, int kh, int kw, int stride, int pad,
+                            const ghost_conv_epi* epi, void* y, int ldy, float* stat, void* ws, int64_t ws_bytes,
+                            void* stream);
 /* Conv2d 3x3/p1 to Cout <= 3 channels (the generator's RGB output): halo-tiled per-tap partial
  * sums; w_narrow [32][Kpad], row (ky*3+kx)*Cout + o; optional residual, tanh and BGR uint8 copy. */
 int ghost_conv3x3_narrow_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx, const void* w_narrow,

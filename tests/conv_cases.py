@@ -55,3 +55,126 @@ CONVT_EDGES = [
 def gemm_tokens(plan, t):
     """The tokens the GEMM line must hold for storage type name ``t`` ("bf16" / "f16")."""
     return plan + ("t=" + t,) if plan[0] == "glds" else plan
+
+
+# ----------------------------------------------------------------------------------------
+# The convolution families off the implicit GEMM: halo, halo_pp, convT_halo, s2_patch, first, stem3x3.  One entry per
+# variant, each at the smallest shape that selects it (halo_plan wants 64 work items, convT_halo 128 workgroups,
+# s2_patch 32), with the tokens its plan-log line must hold.  tests/test_conv_ops.py runs them on the GPU against a
+# float64 reference, tests/test_conv_plan_cpu.py asks ghost_conv_plan (ncu = 256) for the same tokens without one.
+# The rule above holds here too: if a retuned heuristic moves a case, change the shape, not the class.
+# ----------------------------------------------------------------------------------------
+RES, RES_FIRST, PRELU, Y2, TANH, IN_PART = 1, 2, 4, 8, 32, 64      # GHOST_CONV_PLAN_* (include/ghost_amd.h)
+
+# epilogues (include/ghost_amd.h ghost_conv_epi): bn = per-channel scale and shift; slope is the leaky slope where no
+# PReLU table is given; res = a residual, added after the activation unless res_first
+MODES = {
+    "bn": dict(bn=1, slope=0.2),                                  # scale / shift / leaky
+    "res": dict(bn=0, slope=1.0, res=1),                          # AAD_ResBlk's conv + residual: nothing else
+    "none": dict(bn=0, slope=1.0),                                # ... and without it
+    "y2": dict(bn=1, slope=0.2, y2=1),
+    "prelu_y2": dict(bn=1, slope=1.0, prelu=1, y2=1),             # IBasicBlock conv1 + the next BN
+    "prelu_res_y2": dict(bn=1, slope=1.0, prelu=1, res=1, y2=1),
+    "resfirst": dict(bn=1, slope=0.0, res=1, res_first=1),        # Bottleneck tail relu(bn(conv) + residual)
+    "resfirst_y2": dict(bn=1, slope=1.0, res=1, res_first=1, y2=1),   # IBasicBlock conv2 + residual + the next BN
+    "tanh": dict(bn=1, slope=1.0, tanh=1),
+    "bn_res": dict(bn=1, slope=0.2, res=1),                       # the linknet deconv: BN + leaky, then the skip
+}
+
+
+def mode_flags(mode):
+    m = MODES[mode]
+    return (RES if m.get("res") else 0) | (RES_FIRST if m.get("res_first") else 0) | (PRELU if m.get("prelu") else 0) | \
+           (Y2 if m.get("y2") else 0) | (TANH if m.get("tanh") else 0)
+
+
+LDY_PAD = 8
+T16 = ("bf16", "f16")
+
+
+def _case(tokens, B, H, W, cin, n, mode="bn", k=3, s=1, p=1, kind="fwd", ldx=None, ldy=None, types=T16, stats=False):
+    """tokens: the kernel's name first, then what its line must hold (t=<type> is added per type).  ldx > cin: the
+    input is a channel slice of a wider buffer whose other channels hold finite junk (the 3-channel convs' 4-channel
+    layout: the kernel reads channel 3 against zero weights).  stats: through ghost_conv2d_stats_nhwc."""
+    return dict(tokens=tuple(tokens), B=B, H=H, W=W, cin=cin, n=n, mode=mode, k=k, s=s, p=p, kind=kind,
+                ldx=cin if ldx is None else ldx, ldy=n + LDY_PAD if ldy is None else ldy, types=tuple(types),
+                stats=stats)
+
+
+def _pp(tile, resw, ncb, n, overhang, uneven=0):
+    return ("halo_pp", f"tile={tile}", f"RESW={resw}", "STATS=0", f"NCB={ncb}", f"N={n}", f"overhang={overhang}",
+            f"uneven={uneven}")
+
+
+def _halo(tile, cin, n, overhang):
+    return ("halo", f"tile={tile}", f"Cin={cin}", f"N={n}", f"overhang={overhang}")
+
+
+_SWEEP = (64, 128, 192, 256, 512, 1024)        # the persistent kernels' Cin set: NCB 2, 4, 6, 8, 16, 32
+_WIDE_MODE = {64: "bn", 128: "res", 192: "none", 256: "bn", 512: "res", 1024: "none"}
+
+FAMILY_CASES = (
+    # halo_pp tile=Wide: exact 16 x 32 tiles.  32 samples of one tile x 2 channel blocks = 64 work items; the three
+    # epilogue forms of the kernel (scale / shift / leaky, residual alone, nothing) alternate over the NCB sweep
+    [_case(_pp("Wide", 0, c // 32, 128, 0), 32, 16, 32, c, 128, _WIDE_MODE[c], ldx=c + 8 * (c == 128)) for c in _SWEEP] +
+    [_case(_pp("Wide", 1, 2, 64, 0), 64, 16, 32, 64, 64, "bn"),
+     # 33 x 8 tiles = 264 work items on 256 CUs
+     _case(_pp("Wide", 1, 2, 64, 0, uneven=1), 33, 64, 64, 64, 64, "res")] +
+    # halo_pp tile=Img8: four whole 8 x 8 images per tile
+    [_case(_pp("Img8", 1, 2, 64, 0), 4, 8, 8, 64, 64, "res")] +
+    [_case(_pp("Img8", 0, c // 32, 128, 0), 4, 8, 8, c, 128, "bn" if c in (64, 512) else "none" if c == 256 else "res")
+     for c in (64, 128, 256, 512, 1024)] +
+    # halo_pp tile=Small: 16 x 16 tiles over a 14 x 14 image; overhang=0 only through the epilogue rule
+    [_case(_pp("Small", int(c == 64), c // 32, 64, 1), 64, 14, 14, c, 64, "bn" if c != 128 else "res") for c in _SWEEP] +
+    [_case(_pp("Small", 1, 2, 64, 0), 8, 48, 48, 64, 64, "prelu_y2", ldx=72),
+     _case(_pp("Small", 0, 4, 64, 0), 64, 16, 16, 128, 64, "resfirst")] +
+    # halo_pp tile=Pair: a 16 x 16 window of two samples (64 pairs x 4 channel blocks = 256 work items)
+    [_case(_pp("Pair", 0, c // 32, 256, 1), 128, 14, 14, c, 256, "bn" if c != 256 else "res") for c in _SWEEP] +
+    [_case(_pp("Pair", 0, 4, 128, 1), 64, 28, 28, 128, 128, "prelu_y2"),
+     _case(_pp("Pair", 0, 4, 128, 1), 64, 28, 28, 128, 128, "resfirst_y2")] +
+    # halo (non-persistent)
+    [_case(_halo("Wide", 96, 128, 0), 16, 32, 32, 96, 128, "bn"),
+     _case(_halo("Wide", 32, 64, 0), 32, 32, 32, 32, 64, "res"),
+     _case(_halo("Wide", 64, 64, 0), 32, 32, 32, 64, 64, "prelu_y2"),
+     _case(_halo("Wide", 64, 64, 0), 32, 32, 32, 64, 64, "tanh"),
+     _case(_halo("Wide", 64, 64, 0), 32, 32, 32, 64, 64, "bn", ldy=68),        # ldy % 8 != 0: the 8-byte stores
+     _case(_halo("Wide", 64, 576, 0), 4, 32, 32, 64, 576, "bn", ldx=72),       # N > 512
+     _case(_halo("Small", 64, 64, 0), 64, 16, 16, 64, 64, "bn"),
+     _case(_halo("Small", 96, 128, 1), 8, 28, 28, 96, 128, "res"),
+     _case(_halo("Small", 64, 576, 1), 8, 14, 14, 64, 576, "none")] +
+    # convT_halo: 4x4/s2/p1 deconv on 8 x 16 input tiles, 128 workgroups
+    [_case(("convT_halo", "BN=64", "Cin=64", "N=128", "res=0"), 64, 8, 16, 64, 128, "bn", kind="T", ldy=160),
+     _case(("convT_halo", "BN=64", "Cin=96", "N=128", "res=1"), 32, 16, 16, 96, 128, "res", kind="T", ldx=104),
+     _case(("convT_halo", "BN=32", "Cin=64", "N=32", "res=0"), 128, 8, 16, 64, 32, "none", kind="T"),
+     _case(("convT_halo", "BN=32", "Cin=32", "N=32", "res=1"), 32, 16, 32, 32, 32, "bn_res", kind="T")] +
+    # s2_patch: 4x4/s2 and 3x3/s2 on 8 x 16 output tiles
+    [_case(("s2_patch", "K=4", "ncb=1", "N=64", "overhang=0"), 32, 16, 32, 32, 64, "bn", k=4, s=2, ldx=64),
+     _case(("s2_patch", "K=4", "ncb=2", "N=128", "overhang=0"), 2, 64, 64, 64, 128, "none", k=4, s=2),
+     _case(("s2_patch", "K=3", "ncb=2", "N=64", "overhang=0"), 4, 16, 32, 64, 64, "bn", s=2),
+     _case(("s2_patch", "K=3", "ncb=1", "N=64", "overhang=1"), 1, 14, 28, 32, 64, "resfirst", s=2),
+     _case(("s2_patch", "K=3", "ncb=2", "N=128", "overhang=1"), 2, 28, 28, 64, 128, "prelu_res_y2", s=2)] +
+    # first: the encoder's 3 -> 32 4x4/s2; MFMA on the 4-channel layout where Wo % 64 == 0 (M = 64: one chunk of a
+    # wave's share; M = 1024: whole shares), else the scalar kernel (also in fp32)
+    [_case(("first", "mfma", "chunktail=1"), 1, 2, 128, 3, 32, "bn", k=4, s=2, ldx=4),
+     _case(("first", "mfma", "chunktail=0"), 1, 32, 128, 3, 32, "bn", k=4, s=2, ldx=4),
+     _case(("first", "scalar", "mtail=1"), 1, 6, 10, 3, 32, "bn", k=4, s=2, ldx=3, types=T16 + ("f32",)),
+     _case(("first", "scalar", "mtail=0"), 2, 16, 64, 3, 32, "bn", k=4, s=2, ldx=4, types=T16 + ("f32",))] +
+    # stem3x3: ArcFace's 3 -> 64 on the 4-channel layout (bf16 only)
+    [_case(("stem3x3", "y2=1", "mtail=1", "chunktail=1"), 2, 9, 9, 3, 64, "prelu_y2", ldx=4, types=("bf16",)),
+     _case(("stem3x3", "y2=0", "mtail=0", "chunktail=0"), 1, 32, 32, 3, 64, "bn", ldx=4, types=("bf16",)),
+     _case(("stem3x3", "y2=1", "mtail=0", "chunktail=1"), 1, 8, 8, 3, 64, "y2", ldx=4, types=("bf16",))]
+)
+# every tile=Wide and tile=Img8 row again with the InstanceNorm partials (STATS=1)
+FAMILY_CASES += [dict(c, stats=True, tokens=tuple("STATS=1" if t == "STATS=0" else t for t in c["tokens"]))
+                 for c in FAMILY_CASES if c["tokens"][0] == "halo_pp" and c["tokens"][1] in ("tile=Wide", "tile=Img8")]
+
+
+def case_id(c):
+    return "-".join([c["tokens"][0], c["tokens"][1].replace("tile=", "").replace("=", "")] +
+                    [f"B{c['B']}", f"{c['H']}x{c['W']}", f"{c['cin']}to{c['n']}", c["mode"]] +
+                    ([f"ldy{c['ldy']}"] if c["ldy"] != c["n"] + LDY_PAD else []) + (["stats"] if c["stats"] else []))
+
+
+def case_tokens(c, t):
+    """The tokens of the case's line for storage type name ``t``."""
+    return c["tokens"] + ("t=" + t,)

@@ -82,6 +82,31 @@ def test_convT_edge_signatures(lib, dt, cout, tokens):
     assert [l.split()[0] for l in lines[1:]] == ["splitk_reduce4"], lines
 
 
+def _family_rows():
+    return [pytest.param(c, t, id=f"{K.case_id(c)}-{t}") for c in K.FAMILY_CASES for t in c["types"]]
+
+
+@pytest.mark.parametrize("c,t", _family_rows())
+def test_family_case_signatures(lib, c, t):
+    """What test_conv_ops.py asserts of the plan log on the GPU: every case of the families off the implicit GEMM
+    gives one line, its kernel's with its tokens, and needs no workspace (first: its 6 KB of fp32 weights).  The
+    STATS twins ask with the InstanceNorm partials set, as ghost_conv2d_stats_nhwc launches them."""
+    dt = {"bf16": BF16, "f16": F16, "f32": F32}[t]
+    flags = K.mode_flags(c["mode"]) | (IN_PART if c["stats"] else 0)
+    lines, ws = plan(lib, dt, c["B"], c["H"], c["W"], c["cin"], c["n"], c["k"], c["s"], c["p"],
+                     kind=T4S2 if c["kind"] == "T" else FWD, ldx=c["ldx"], ldy=c["ldy"], flags=flags)
+    assert lines and len(lines) == 1, lines
+    assert lines[0].split()[0] == c["tokens"][0] and has(lines[0], *K.case_tokens(c, t)), (c["tokens"], lines)
+    assert ws == (32 * 48 * 4 if c["tokens"][0] == "first" else 0), ws
+
+
+def test_family_cases_cover_both_types_and_are_distinct():
+    ids = [K.case_id(c) for c in K.FAMILY_CASES]
+    assert len(set(ids)) == len(ids), sorted(i for i in ids if ids.count(i) > 1)
+    for c in K.FAMILY_CASES:
+        assert set(c["types"]) >= ({"bf16"} if c["tokens"][0] == "stem3x3" else {"bf16", "f16"}), c
+
+
 # ----------------------------------------------------------------------------------------
 # replay of DESIGN.md section 2a: the attribute encoder's 13 convolutions, as the parent launchers logged them on
 # the MI355X

@@ -71,7 +71,10 @@ def nhwc(x):
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("cin,cout,k,s,p,H", [(32, 64, 4, 2, 1, 32), (3, 32, 4, 2, 1, 64), (64, 64, 3, 1, 1, 40),
                                               (128, 3, 3, 1, 1, 32), (96, 200, 1, 1, 0, 9),
-                                              # halo-tiled 3x3 kernel shapes (bf16, H % 16, W % 32, N % 64)
+                                              # 3x3 shapes of the halo kernels' form (bf16, H % 16, W % 32, N % 64);
+                                              # at B = 2 they are 4 to 16 work items, under halo_plan's 64, so
+                                              # bf16 runs the implicit GEMM's split path (igemm / glds epi=SPLIT +
+                                              # splitk_reduce4); the halo kernels: tests/test_conv_ops.py
                                               (64, 64, 3, 1, 1, 64), (96, 128, 3, 1, 1, 32), (256, 64, 3, 1, 1, 32),
                                               (128, 192, 3, 1, 1, 16)])
 def test_conv2d_op(lib, dt, cin, cout, k, s, p, H):
@@ -107,9 +110,11 @@ def test_conv2d_op(lib, dt, cin, cout, k, s, p, H):
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("H,B", [(256, 2), (256, 1), (64, 3), (128, 1)])
 def test_conv3x3_64_op(lib, dt, H, B):
-    """The persistent halo conv at 64 -> 64 with resident weights (AADBlk8's first conv at 256 x 256) against
-    torch's fp32 conv of the same 16-bit operands, bf16 and fp16 storage; B = 1 at 128 x 128 and B = 3 at
-    64 x 64 give workgroups with uneven tile counts."""
+    """64 -> 64 3x3 against torch's fp32 conv of the same 16-bit operands, bf16 and fp16 storage.  The 256 x 256
+    cases (AADBlk8's first conv) run the persistent halo conv with resident weights (halo_pp tile=Wide RESW=1,
+    uneven=0); B = 1 at 128 x 128 and B = 3 at 64 x 64 are 32 and 24 work items, under halo_plan's 64, and run the
+    implicit GEMM's split path (igemm 256x64x32 epi=SPLIT + splitk_reduce4).  Uneven tile counts per workgroup:
+    tests/test_conv_ops.py (conv_cases.FAMILY_CASES, uneven=1)."""
     from ghost_amd import _lib
     from ghost_amd.network.pack import pack_conv, rup
     g = torch.Generator().manual_seed(H + B)
@@ -139,9 +144,11 @@ def test_conv3x3_64_op(lib, dt, H, B):
                                                  (128, 256, 32, 3, 128, 256, True), (32, 64, 64, 1, 0, 0, False),
                                                  (256, 64, 32, 2, 256, 0, True)])
 def test_conv4x4s2_patch_kernel(lib, cin, cout, H, B, xoff, yoff, bn):
-    """The encoder's 4x4/s2 convs with Cin % 32 == 0 (conv2..conv4) on the LDS input-patch kernel: the input read
-    from a channel slice of a 2*Cin-wide buffer (the unet concat layout) and the output written into a channel
-    slice of a wider buffer, against torch's fp32 conv of the same bf16 operands."""
+    """The encoder's 4x4/s2 convs with Cin % 32 == 0 (conv2..conv4): the input read from a channel slice of a
+    2*Cin-wide buffer (the unet concat layout) and the output written into a channel slice of a wider buffer,
+    against torch's fp32 conv of the same bf16 operands.  Only 64 -> 128 at 64 x 64 has the LDS input-patch
+    kernel's 32 workgroups (s2_patch K=4 ncb=2); the other four run the implicit GEMM's split path (glds / igemm
+    epi=SPLIT + splitk_reduce4) on the same slices.  The patch kernel's variants: tests/test_conv_ops.py."""
     from ghost_amd import _lib
     from ghost_amd.network.pack import pack_conv, rup
     dt = torch.bfloat16
@@ -185,16 +192,18 @@ def test_conv4x4s2_patch_kernel(lib, cin, cout, H, B, xoff, yoff, bn):
     (64, 64, 32, 1, 2, 0, 16, "relu"),        # Bottleneck conv1 1x1/s2
     (128, 128, 512, 1, 2, 0, 16, "none"),     # downsample 1x1/s2 + BN
     (32, 32, 128, 1, 1, 0, 16, "res_relu"),   # Bottleneck tail relu(bn3(conv3) + residual)
-    (64, 64, 64, 3, 1, 1, 28, "prelu_y2"),    # IBasicBlock conv + BN + PReLU, with a BN'd second output
+    (64, 64, 64, 3, 1, 1, 28, "prelu_y2"),    # IBasicBlock conv + BN + PReLU, with a BN'd second output (the GEMM)
     (64, 64, 128, 3, 2, 1, 28, "res_y2"),     # IBasicBlock conv2/s2 + BN + residual, second output = next BN
-    # 3x3/s1 shapes the halo kernel takes in bf16 with overhanging 16x16 tiles (ArcFace stages)
-    (64, 64, 64, 3, 1, 1, 112, "prelu_y2"),   # layer1 block-0 conv1 at 112x112 (7 x 7 exact tiles)
-    (64, 64, 128, 3, 1, 1, 56, "prelu_y2"),   # layer2 block-0 conv1 at 56x56
-    (128, 128, 128, 3, 1, 1, 28, "res_y2"),   # layer2 conv2 + residual + next BN
-    (256, 256, 256, 3, 1, 1, 14, "prelu_y2"), # layer3 conv1
-    (256, 256, 256, 3, 1, 1, 14, "res_y2"),   # layer3 conv2
-    (64, 64, 64, 3, 1, 1, 48, "res_relu"),    # residual before the activation on the halo path
-    (512, 512, 512, 3, 1, 1, 7, "res_y2"),    # 7x7 stays on the implicit GEMM
+    # 3x3/s1 shapes of the ArcFace stages.  At B = 2 only 112 x 112 and 56 x 56 have halo_plan's 64 work items (bf16:
+    # halo_pp tile=Small); the others run the implicit GEMM's split path (glds / igemm epi=SPLIT + splitk_reduce4)
+    # with the IBasicBlock epilogues.  The halo kernels' variants and epilogues: tests/test_conv_ops.py
+    (64, 64, 64, 3, 1, 1, 112, "prelu_y2"),   # layer1 block-0 conv1 at 112x112 (7 x 7 exact tiles): halo_pp Small
+    (64, 64, 128, 3, 1, 1, 56, "prelu_y2"),   # layer2 block-0 conv1 at 56x56: halo_pp Small, overhanging tiles
+    (128, 128, 128, 3, 1, 1, 28, "res_y2"),   # layer2 conv2 + residual + next BN (the GEMM)
+    (256, 256, 256, 3, 1, 1, 14, "prelu_y2"), # layer3 conv1 (the GEMM's deep ring)
+    (256, 256, 256, 3, 1, 1, 14, "res_y2"),   # layer3 conv2 (the GEMM's deep ring)
+    (64, 64, 64, 3, 1, 1, 48, "res_relu"),    # residual before the activation (18 work items: the GEMM)
+    (512, 512, 512, 3, 1, 1, 7, "res_y2"),    # 7x7 stays on the implicit GEMM at every batch
     (3, 4, 64, 3, 1, 1, 112, "prelu_y2"),     # ArcFace stem (bf16: the 4-channel MFMA stem kernel)
     (3, 4, 64, 3, 1, 1, 9, "prelu_y2"),       # stem with a partial last 64-pixel chunk (B*81 = 162)
     # 3x3/s2 on the LDS input-patch kernel in bf16 (conv_s2.hip, 8 x 16 output tiles overhanging 56/28/14)
@@ -302,10 +311,13 @@ def test_first_conv_padded_input(lib, dt):
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("cin,cout,H,ldy_extra,skip_add", [(64, 32, 8, 32, False), (1024, 1024, 2, 1024, False),
                                                            (128, 64, 16, 0, True), (32, 48, 5, 16, False),
-                                                           # halo ConvT shapes (bf16): N = 32 slice, two N tiles
+                                                           # shapes of convT_halo's form (bf16: N = 32 slice, two
+                                                           # N tiles); at B = 2 they are 4 and 32 workgroups, under
+                                                           # its 128, and run the implicit GEMM unsplit
                                                            (64, 32, 16, 32, False), (96, 128, 32, 64, False)])
 def test_convT_op(lib, dt, cin, cout, H, ldy_extra, skip_add):
-    """ConvT4x4/s2/p1 + BN + LReLU, written into a channel slice (unet concat) or + skip (linknet)."""
+    """ConvT4x4/s2/p1 + BN + LReLU, written into a channel slice (unet concat) or + skip (linknet).  Every case runs
+    the implicit GEMM (kind=T4S2, split and unsplit); convT_halo needs 128 workgroups: tests/test_conv_ops.py."""
     from ghost_amd import _lib
     from ghost_amd.network.pack import pack_convT4x4, rup
     g = torch.Generator().manual_seed(cin + H)
