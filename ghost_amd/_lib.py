@@ -105,6 +105,16 @@ _SIGS = {
                                         vp]),
     "ghost_norm_modulate_nhwc": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, f32, i32, vp, i32, vp]),
     "ghost_lip_pool_nhwc": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
+    "ghost_lmk_create": (i32, [i32, C.POINTER(vp)]),
+    "ghost_lmk_destroy": (None, [vp]),
+    "ghost_lmk_bind": (i32, [vp, C.c_char_p, vp, i64]),
+    "ghost_lmk_missing": (i32, [vp]),
+    "ghost_lmk_workspace_bytes": (i64, [vp, i32]),
+    "ghost_lmk_forward": (i32, [vp, vp, i64, i32, i32, vp, vp, i64, vp]),
+    "ghost_lmk_landmarks_u8": (i32, [vp, vp, i64, i32, vp, vp, vp, i64, vp]),
+    "ghost_lmk_set_taps": (i32, [vp, C.POINTER(vp), i32]),
+    "ghost_dwsep_block_nhwc": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp,
+                                     vp, i32, vp, i32, vp]),
     "ghost_plan_log": (i32, [i32]),
     "ghost_plan_log_read": (i64, [C.c_char_p, i64]),
     "ghost_aad_plan": (i64, [i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, C.POINTER(i32), C.c_char_p, i64]),

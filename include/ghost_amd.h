@@ -318,6 +318,50 @@ int ghost_arc_set_taps(ghost_arc* h, void* const* taps, int ntaps);
 int ghost_arc_match(const float* face_emb, int F, const float* target_emb, int T, int dim, float similarity_th,
                     int32_t* best_idx, float* best_sim, int32_t* accepted, void* stream);
 
+/* ---- 106-point face landmarks (insightface 2d106det, the `handler` GHOST builds its masks from) --------
+ * Replaces: coordinate_reg/image_infer.py:141-157 Handler.get_without_detection_without_transform, called per face by
+ *   utils/inference/video_processing.py:218-223.  The network is coordinate_reg/model/2d106det-symbol.json
+ *   (MobileNet-v1 at width 0.5 on a 192 x 192 RGB crop, BatchNorm(fix_gamma) + per-channel PReLU after every conv).
+ *   No checkpoint and no mxnet offline: parity against mxnet is unpinned.
+ * dtype: storage of activations and of the pointwise / conv_15 weights (f32, bf16 or f16); the stem, every depthwise
+ * conv, every BatchNorm / PReLU and the fc are fp32 arithmetic on fp32 parameters in all three.
+ * Slots (ghost_amd/landmarks/pack.py): stem.w [27][16] f32; cK.dw.w [9][Cin] f32 and cK.pw.w [rup(Cout,128)][rup(Cin,32)]
+ * dtype for K = 2..14; c15.w as every conv here; X.scale / X.shift / X.prelu f32 for X in {stem, cK.dw, cK.pw, c15};
+ * fc.w [576][212] f32 with K = (y*3 + x)*64 + c; fc.bias [212] f32.  Every slot must be 16-byte aligned. */
+typedef struct ghost_lmk ghost_lmk;
+int ghost_lmk_create(int dtype, ghost_lmk** out);
+void ghost_lmk_destroy(ghost_lmk* h);
+int ghost_lmk_bind(ghost_lmk* h, const char* name, const void* dev_ptr, int64_t numel);
+int ghost_lmk_missing(ghost_lmk* h);
+int64_t ghost_lmk_workspace_bytes(ghost_lmk* h, int N);
+/* the network alone: x192 uint8 [N,192,192,3], x_batch_stride bytes apart, channel order B,G,R (bgr != 0) or R,G,B
+ * -> pred fp32 [N,212] (fc1's output).  N == 0 returns GHOST_OK without a launch; N <= 65535. */
+int ghost_lmk_forward(ghost_lmk* h, const uint8_t* x192, int64_t x_batch_stride, int bgr, int N, float* pred, void* ws,
+                      int64_t ws_bytes, void* stream);
+/* get_without_detection_without_transform over a batch: crops224_bgr uint8 [N,224,224,3] -> cv2.warpAffine(crop, M,
+ * (192, 192), borderValue=0.0) with M = [[0.57142857, 0, 32], [0, 0.57142857, 32]] (ghost_align_crops_u8's bytes) ->
+ * BGR to RGB -> the network -> landmarks fp32 [N,106,2] = ((pred + 1) * 96) * 1.75 - 56 in the crop's pixel
+ * coordinates.  pred (optional) receives fc1's output [N,212]. */
+int ghost_lmk_landmarks_u8(ghost_lmk* h, const uint8_t* crops224_bgr, int64_t crop_batch_stride, int N, float* landmarks,
+                           float* pred, void* ws, int64_t ws_bytes, void* stream);
+/* Diagnostic taps: while set (ntaps = 4), every forward copies the stored outputs of conv_2 [N,96,96,32], conv_7
+ * [N,12,12,256], conv_14 [N,6,6,512] and conv_15 [N,3,3,64] (NHWC, handle dtype) into the non-NULL taps[i].
+ * ntaps = 0 clears them. */
+int ghost_lmk_set_taps(ghost_lmk* h, void* const* taps, int ntaps);
+/* One depthwise-separable block: d = PReLU(BN(depthwise3x3(x, stride 1 | 2, pad 1))) in fp32 from fp32 weights dw_w
+ * [9][Cin] (tap ky*3 + kx), rounded once to dtype; y = PReLU(BN(d * w^T)) with the 1x1 on the matrix cores, fp32
+ * accumulation and epilogue.  BN is v*scale[c] + shift[c], PReLU v > 0 ? v : v*prelu[c]; dw_* have Cin entries, scale /
+ * shift / prelu Cout.  w_packed: [>= Cout][Kpad] of dtype, K = input channel, zero beyond Cin (Kpad % 32 == 0: pack_conv
+ * of the 1x1 weight).  x [B,H,W,ldx], y [B,Ho,Wo,ldy], Ho = (H - 1) / stride + 1.
+ * dw_tap (optional, [B,Ho,Wo,ld_tap]): also receives d; y is bit-identical with and without it.
+ * Cout == 0: depthwise only, d is written to y (w_packed / scale / shift / prelu / dw_tap unused, dw_tap must be NULL).
+ * GHOST_EINVAL: Cin % 8, Cout % 16 (Cout % 128 above 128), Cin > 992 with Cout > 0 (the LDS image), a pointer or
+ * leading dimension that is not 16-byte aligned or is below its channel count. */
+int ghost_dwsep_block_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, int ldx, int stride,
+                           const float* dw_w, const float* dw_scale, const float* dw_shift, const float* dw_prelu,
+                           const void* w_packed, int Cout, int Kpad, const float* scale, const float* shift,
+                           const float* prelu, void* y, int ldy, void* dw_tap, int ld_tap, void* stream);
+
 /* ---- paste-back blend (get_final_video, utils/inference/video_processing.py:218-227) ----
  * For each frame f with valid[f] != 0 (valid may be NULL): warp the crop-space swap [Hs,Ws,3] u8 and
  * mask [Hs,Ws] f32 back into the frame with kornia.warp_affine semantics (bilinear, zeros,
