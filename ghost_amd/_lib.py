@@ -77,6 +77,7 @@ _SIGS = {
     "ghost_mask_polygons": (i32, [vp, i32, i32, vp, vp, vp]),
     "ghost_face_masks_workspace_bytes": (i64, [i32, i32, i32]),
     "ghost_face_masks": (i32, [vp, vp, vp, i32, i32, i32, vp, i64, vp, i64, vp]),
+    "ghost_mask_polygons_dev": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp]),
     "ghost_conv2d_ex_nhwc": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp,
                                    i32, vp, i64, vp]),
     "ghost_conv2d_stats_nhwc": (i32, [i32, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp,

@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib
 from ..inference.blend import resize_u8
-from ..inference.masks import face_masks, mask_params
+from ..inference.masks import _raster, face_masks, mask_params, mask_polygons_device
 
 
 class Handler:
@@ -66,6 +66,60 @@ def identity_masks(net, swaps256_u8: torch.Tensor, crops224_u8: torch.Tensor, pr
     lm_all, params, idx = identity_landmarks(net, swaps, crops224_u8, pres)
     if len(idx):
         masks[torch.from_numpy(idx).to(dev)] = face_masks(lm_all[idx], params[idx], H, W, dev)
+    return masks, swaps, lm_all, params
+
+
+def run_indices(present: Sequence):
+    """Host-side index arrays of ``identity_masks_device``, from ``present`` alone: ``idx`` int64 [P] the present
+    frames, ``starts`` int64 [R] the first frame of every run (``present_runs``), and per present frame k (int32 [P])
+    ``ref_index[k]`` the position in ``idx`` of the first frame of k's run (so ``idx[ref_index[k]]`` is that frame)
+    and ``tgt_index[k]`` the number of k's run: where the landmarks of the present swaps and of the runs' first
+    target crops stand in the two batches the network is given."""
+    pres = np.asarray(present).astype(bool).reshape(-1)
+    idx = np.flatnonzero(pres).astype(np.int64)
+    prev = np.concatenate([[False], pres[:-1]])
+    first = (pres & ~prev)[idx]                       # per present frame: it starts a run
+    starts = idx[first]
+    tgt_index = (np.cumsum(first) - 1).astype(np.int32)
+    ref_index = np.flatnonzero(first).astype(np.int32)[tgt_index] if len(idx) else np.zeros(0, np.int32)
+    return idx, starts, ref_index, tgt_index
+
+
+def identity_masks_device(net, swaps256_u8: torch.Tensor, crops224_u8: torch.Tensor, present, H: int = 224,
+                          W: int = 224):
+    """``identity_masks`` without the round trip: the same inputs (``present`` is host data) and the same masks,
+    swaps, landmarks and params bit for bit, with ``landmarks`` (float32 [F,106,2]) and ``params`` (int32 [F,3])
+    device tensors, zero on absent frames.
+
+    The parameter choice, the eyebrow expansion and the convex hull run in one launch on the landmarks where the
+    network left them (ghost_mask_polygons_dev); only the index arrays of ``run_indices`` go up, without waiting.
+    Between entry and return nothing is copied to the host and nothing synchronises."""
+    _lib.require_gpu(swaps256_u8, "identity_masks_device")
+    _lib.require_gpu(crops224_u8, "identity_masks_device")
+    if torch.is_tensor(present) and present.is_cuda:
+        raise RuntimeError("ghost_amd: identity_masks_device takes present as host data (a device tensor would "
+                           "have to be copied back)")
+    dev = swaps256_u8.device
+    F_ = swaps256_u8.shape[0]
+    pres = np.asarray(present).astype(bool).reshape(-1)
+    if pres.shape[0] != F_ or crops224_u8.shape[0] != F_:
+        raise RuntimeError("ghost_amd: identity_masks_device needs F swaps, F crops and F present flags")
+    swaps = swaps256_u8 if tuple(swaps256_u8.shape[1:3]) == (224, 224) else resize_u8(swaps256_u8, (224, 224))
+    masks = torch.zeros(F_, H, W, dtype=torch.float32, device=dev)
+    lm_all = torch.zeros(F_, 106, 2, dtype=torch.float32, device=dev)
+    params = torch.zeros(F_, 3, dtype=torch.int32, device=dev)
+    idx, starts, ref_index, tgt_index = run_indices(pres)
+    if not len(idx):
+        return masks, swaps, lm_all, params
+    d_idx, d_starts, d_ref, d_tgt = (torch.from_numpy(a).to(dev, non_blocking=True)
+                                     for a in (idx, starts, ref_index, tgt_index))
+    lm_sw = net.landmarks_u8(swaps.index_select(0, d_idx)).contiguous()
+    lm_tg = net.landmarks_u8(crops224_u8.index_select(0, d_starts)).contiguous()
+    poly, nv, pr = mask_polygons_device(lm_sw, landmarks_ref=lm_sw, ref_index=d_ref, landmarks_tgt=lm_tg,
+                                        tgt_index=d_tgt)
+    masks.index_copy_(0, d_idx, _raster(poly, nv, pr, H, W, None))
+    lm_all.index_copy_(0, d_idx, lm_sw)
+    params.index_copy_(0, d_idx, pr)
     return masks, swaps, lm_all, params
 
 

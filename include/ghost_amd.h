@@ -481,6 +481,19 @@ int ghost_mask_polygons(const float* landmarks, int F, int npts, const int32_t* 
 int64_t ghost_face_masks_workspace_bytes(int F, int H, int W);
 int ghost_face_masks(const int32_t* poly, const int32_t* nv, const int32_t* params, int F, int H, int W, float* masks,
                      int64_t mask_stride, void* ws, int64_t ws_bytes, void* stream);
+/* Device (csrc/mask_poly.hip): what ghost_mask_polygons and face_mask_static's parameter choice compute on the host,
+ * in one launch for F faces and equal to them bit for bit, so that poly / nv / params for ghost_face_masks are
+ * produced without a device -> host copy.  Every pointer is a device pointer.  landmarks [F][106][2] f32 (finite,
+ * |v| <= 2^20).  Exactly one of two forms: params_in [F][3] given (used as they are; the four reference arguments
+ * null), or params_in null and all of landmarks_ref [n_ref][106][2], ref_index [F], landmarks_tgt [n_tgt][106][2],
+ * tgt_index [F] given: face f's (erode, sigmaX, sigmaY) are masks.py:43-65 of landmarks_ref[ref_index[f]] (the swap's
+ * landmarks) and landmarks_tgt[tgt_index[f]] (the target crop's), in fp32 in numpy's order; an index outside its set
+ * yields params 0, 0, 0.  Anything else is GHOST_EINVAL.  Writes params_out [F][3] (the chosen parameters in either
+ * form), poly [F][128][2] (zero from nv[f] on) and nv [F].  F = 0 returns GHOST_OK without a launch.  The call
+ * neither allocates nor synchronises. */
+int ghost_mask_polygons_dev(const float* landmarks, const int32_t* params_in, const float* landmarks_ref,
+                            const int32_t* ref_index, int n_ref, const float* landmarks_tgt, const int32_t* tgt_index,
+                            int n_tgt, int32_t* params_out, int32_t* poly, int32_t* nv, int F, void* stream);
 
 /* ---- plan log (test support) ----
  * While enabled, every launcher that chooses among kernel variants by shape (the conv dispatcher and everything
