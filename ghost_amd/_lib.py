@@ -120,6 +120,24 @@ _SIGS = {
     "ghost_plan_log_read": (i64, [C.c_char_p, i64]),
     "ghost_aad_plan": (i64, [i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, C.POINTER(i32), C.c_char_p, i64]),
     "ghost_conv_plan": (i64, [i32] * 22 + [C.POINTER(i64), C.c_char_p, i64]),
+    "ghost_det_create": (i32, [i32, i32, i32, C.POINTER(vp)]),
+    "ghost_det_destroy": (None, [vp]),
+    "ghost_det_bind": (i32, [vp, C.c_char_p, vp, i64]),
+    "ghost_det_missing": (i32, [vp]),
+    "ghost_det_workspace_bytes": (i64, [vp, i32]),
+    "ghost_det_plan": (i64, [vp, i32, C.c_char_p, i64]),
+    "ghost_det_forward_u8": (i32, [vp, vp, i64, i32, i32, i32, i32, i32, C.POINTER(vp), vp, i64, vp]),
+    "ghost_det_detect_u8": (i32, [vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, f32, i32, vp, vp, vp, vp, vp, i64,
+                                  vp]),
+    "ghost_det_set_taps": (i32, [vp, C.POINTER(vp), i32]),
+    "ghost_det_letterbox_u8": (i32, [vp, i64, i32, i32, i32, i32, i32, vp, i32, i32, vp]),
+    "ghost_det_stem_u8": (i32, [i32, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "ghost_maxpool3x3s2_nhwc": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
+    "ghost_upsample2x_add_nhwc": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
+    "ghost_det_head_nhwc": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "ghost_det_decode_workspace_bytes": (i64, [i32, i32]),
+    "ghost_det_decode_nms": (i32, [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, f32, f32, f32, i32, i32,
+                                   vp, vp, vp, vp, vp, i64, vp]),
 }
 
 

@@ -533,6 +533,62 @@ int64_t ghost_conv_plan(int ti, int to, int kind, int B, int H, int W, int Cin, 
                         int kh, int kw, int stride, int pad, int ldy, int epi, int split_k, int min_wgs, int nsem,
                         int ncu, int flags, int64_t* ws_bytes, char* buf, int64_t cap);
 
+/* ---- SCRFD face detector (insightface scrfd_10g_bnkps) ----
+ * The network, its letterbox and SCRFD.detect's post-processing for F device-resident frames of one size.  dtype:
+ * GHOST_F32 (the default of the Python module), GHOST_F16 or GHOST_BF16 storage of activations and conv weights; det_w,
+ * det_h: multiples of 32.  Slots: "<unit>.w" (packed as ghost_conv2d_nhwc takes it; "backbone.stem.0.w" fp32 [27][28],
+ * K = (ky*3 + kx)*3 + rgb channel) and "<unit>.b" (fp32 bias, padded to 128), <unit> from ghost_amd/detection/pack.py;
+ * per stride s the three output convs as one: "bbox_head.out.<s>.w" fp32 [720][30] (K = (ky*3 + kx)*80 + c; columns cls
+ * 0-1, reg 2-9, kps 10-29), ".b" fp32 [32] and ".m" fp32 [32] (bbox_scale on the reg columns, 1 elsewhere).  The caller
+ * computes the letterbox on the host as SCRFD.detect does: the frame is resized to (new_w, new_h) and placed top-left in
+ * a zero canvas; det_scale = new_h / H. */
+typedef struct ghost_det ghost_det;
+int ghost_det_create(int dtype, int det_w, int det_h, ghost_det** out);
+void ghost_det_destroy(ghost_det* h);
+int ghost_det_bind(ghost_det* h, const char* name, const void* dev_ptr, int64_t numel);
+int ghost_det_missing(ghost_det* h);
+/* sized for ghost_det_detect_u8 (which covers ghost_det_forward_u8); N <= 4096 and N * det_h/2 * det_w/2 < 2^31 */
+int64_t ghost_det_workspace_bytes(ghost_det* h, int N);
+/* the launches of one detect call, one text line each (test support; no device needed): returns the bytes needed */
+int64_t ghost_det_plan(ghost_det* h, int N, char* buf, int64_t cap);
+/* frames_bgr uint8 [F,H,W,3] -> maps[9] = cls (scores, after the sigmoid) [F,Hl,Wl,2], reg [F,Hl,Wl,8] (times
+ * bbox_scale), kps [F,Hl,Wl,20] for strides 8, 16, 32 in that order (cls0..2, reg0..2, kps0..2), NHWC fp32; channel
+ * a*K + k belongs to anchor a.  No synchronisation; F == 0 returns GHOST_OK without a launch. */
+int ghost_det_forward_u8(ghost_det* h, const uint8_t* frames_bgr, int64_t frame_stride, int F, int H, int W, int new_h,
+                         int new_w, float* const* maps, void* ws, int64_t ws_bytes, void* stream);
+/* SCRFD.detect per frame: det [F,max_faces,5] (x1, y1, x2, y2, score, in frame pixels), kps [F,max_faces,5,2], anchor
+ * [F,max_faces] (the kept candidates' indices in the concatenated anchor order, -1 beyond), count [F,2] = (kept boxes,
+ * candidates at or above thresh), all in kept order, zero beyond.  At most 4096 candidates per frame enter the sort (the
+ * first 4096 in anchor order; count reports the true number) and kept boxes past max_faces are dropped (count reports
+ * the true number).  Equal scores go by ascending anchor index. */
+int ghost_det_detect_u8(ghost_det* h, const uint8_t* frames_bgr, int64_t frame_stride, int F, int H, int W, int new_h,
+                        int new_w, float det_scale, float thresh, float nms_thresh, int max_faces, float* det,
+                        float* kps, int32_t* anchor, int32_t* count, void* ws, int64_t ws_bytes, void* stream);
+/* Diagnostic taps: while set (ntaps = 4), every forward copies the stored outputs of the stem after its pool
+ * [N,Hd/4,Wd/4,56], stage 1 [N,Hd/4,Wd/4,56], stage 4 [N,Hd/32,Wd/32,224] and P3 [N,Hd/8,Wd/8,56] (NHWC, handle dtype)
+ * into the non-NULL taps[i]. */
+int ghost_det_set_taps(ghost_det* h, void* const* taps, int ntaps);
+/* The detector's single operators.  letterbox: cv2.resize(frame, (new_w, new_h)) (ghost_resize_u8_linear's bytes) into
+ * the top-left of a zero canvas [F,Hd,Wd,3].  stem: canvas -> (x - 127.5) / 128, R,G,B order (bgr != 0: the canvas is
+ * B,G,R) -> conv 3x3 s2 p1 3 -> 28 + bias + ReLU in fp32, rounded once to dtype, [N,Hd/2,Wd/2,28].  maxpool: 3x3 s2 p1
+ * (the padding never wins), H, W even, C % 4 == 0.  upsample2x_add: y [N,2h,2w,C] = round(y + nearest-x2(x)) in place.
+ * head: a level's cls / reg / kps convs as one 3x3 p1 conv 80 -> 30 in fp32 from fp32 weights (the slots above): v = (acc
+ * + bias[o]) * mul[o], cls = sigmoid(v); fp32 outputs whatever dtype, the storage type of x [N,H,W,80].
+ * decode_nms: the post-processing of ghost_det_detect_u8 on nine given maps (cls holds scores), cap a power of two in
+ * 2..4096; ws of ghost_det_decode_workspace_bytes(F, cap). */
+int ghost_det_letterbox_u8(const uint8_t* frames, int64_t frame_stride, int F, int H, int W, int new_h, int new_w,
+                           uint8_t* canvas, int Hd, int Wd, void* stream);
+int ghost_det_stem_u8(int dtype, const uint8_t* canvas, int64_t batch_stride, int bgr, int N, int Hd, int Wd,
+                      const float* w, const float* bias, void* y, void* stream);
+int ghost_maxpool3x3s2_nhwc(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream);
+int ghost_upsample2x_add_nhwc(int dtype, const void* x, int N, int h, int w, int C, void* y, void* stream);
+int ghost_det_head_nhwc(int dtype, const void* x, int N, int H, int W, const float* w, const float* bias, const float* mul,
+                        float* cls, float* reg, float* kps, void* stream);
+int64_t ghost_det_decode_workspace_bytes(int F, int cap);
+int ghost_det_decode_nms(const float* const* cls, const float* const* reg, const float* const* kps_maps, int F, int Hd,
+                         int Wd, float thresh, float det_scale, float nms_thresh, int cap, int max_faces, float* det,
+                         float* kps, int32_t* anchor, int32_t* count, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
