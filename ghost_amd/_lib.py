@@ -120,6 +120,12 @@ _SIGS = {
     "ghost_plan_log_read": (i64, [C.c_char_p, i64]),
     "ghost_aad_plan": (i64, [i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, C.POINTER(i32), C.c_char_p, i64]),
     "ghost_conv_plan": (i64, [i32] * 22 + [C.POINTER(i64), C.c_char_p, i64]),
+    "ghost_instnorm_plan": (i64, [i32] * 8 + [C.POINTER(i64), C.c_char_p, i64]),
+    "ghost_conv_rt_nhwc": (i32, [i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp,
+                                 vp, i32, vp, i64, vp, i32, vp]),
+    "ghost_aad_layer_rt_nhwc": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp,
+                                      i32, f32, vp, i32, vp, i64, i32, vp, i32, vp]),
+    "ghost_instnorm_stats_rt_nhwc": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp, i32, vp]),
     "ghost_det_create": (i32, [i32, i32, i32, C.POINTER(vp)]),
     "ghost_det_destroy": (None, [vp]),
     "ghost_det_bind": (i32, [vp, C.c_char_p, vp, i64]),

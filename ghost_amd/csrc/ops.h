@@ -22,6 +22,29 @@ bool in_stats_up2x_closed_form(int dt, int H, int W, int C, int ldx);
 int in_stats_up2x(int dt, const void* x, int ldx, int B, int H, int W, int C, float* stat, void* ws, size_t ws_bytes,
                   hipStream_t s, unsigned* sem = nullptr, int nsem = 0);
 
+// ---- the statistics' plan: which kernel, over which chunks, and how the pass ends, decided once from the shape ----
+// Partial: in_stats_partial_kernel over the tensor's own pixels; PartialUp: the same over the pixels of the virtual
+// upsample; UpQuad: in_stats_up_quad_kernel, the closed form over the source (16-bit, in_stats_up2x_closed_form)
+enum class InStatsKernel { None, Partial, PartialUp, UpQuad };
+// Self: one chunk per (sample, channel group), whose workgroup stores the statistics itself; FinalKernel: partial
+// records, then in_stats_final_kernel; Fused: partial records merged by the last arriver (in_stats_fixup)
+enum class InStatsEnd { Self, FinalKernel, Fused };
+
+struct InStatsPlan {
+  InStatsKernel kernel = InStatsKernel::None;   // None: in_stats / in_stats_up2x refuse the shape (return -1)
+  InStatsEnd end = InStatsEnd::Self;
+  int HW = 0;                                   // pixels the statistics are over (4 H W through the upsample)
+  int chunk = 0, nchunk = 0;                    // pixels per record (UpQuad: 512 source pixels), records per sample
+  unsigned grid[3] = {0, 0, 0}, final_grid = 0;
+  size_t part_bytes = 0;                        // bytes of partial records the launch writes (0 under Self)
+};
+
+// pure: reads integers only; no HIP call.  up2x: H x W is the source of the virtual upsample, else the tensor itself
+// (HW = H * W; only the product matters).  nsem: the arrival counters the caller offers (0: none)
+InStatsPlan in_stats_plan(int dt, int B, int H, int W, int C, int ldx, bool up2x, int nsem);
+// one text line of the plan (test support; the statistics are not in the plan log)
+int in_stats_plan_text(int dt, const InStatsPlan& p, char* buf, size_t cap);
+
 // statistics from the per-(tile, wave) partials a producer kernel wrote (ConvDesc::in_part): nrec
 // records of (mean, centred sum of squares) over 64 pixels per (sample, channel), merged in fp64 (Chan)
 // -> stat = [B][C][2] mean, rstd

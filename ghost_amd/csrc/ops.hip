@@ -378,64 +378,91 @@ bool in_stats_up2x_closed_form(int dt, int H, int W, int C, int ldx) {
   return W % cpb == 0 && H % (512 / cpb) == 0;
 }
 
-template <typename T>
-static void in_stats_launch(const T* x, int ldx, int B, int HW, int C, float* stat, float* part, const Up2xSrc* up,
-                            hipStream_t s, unsigned* sem) {
-  int chunk, nchunk;
-  stats_geometry(B, HW, C, chunk, nchunk);
-  dim3 g1(nchunk, (C + 63) / 64, B);
-  dim3 g2((B * C + 255) / 256);
-  const Up2xSrc u = up ? *up : Up2xSrc{0, 0, 0.f, 0.f};
-  if constexpr (sizeof(T) == 2) {
-    if (up && in_stats_up2x_closed_form(gdt<T>(), u.H, u.W, C, ldx)) {
-      // closed form over the source: (H / 4) * (W / 128) records <= the HW / 512 reserved
-      const int nr = u.H * u.W / 512;   // workgroups of 512 source pixels
-      hipLaunchKernelGGL(in_stats_up_quad_kernel<T>, dim3(nr, C / 64, B), dim3(256), 0, s, x, ldx, C, nr, part, u, stat,
-                         sem);
-      if (!sem)
-        hipLaunchKernelGGL(in_stats_final_kernel<T>, g2, dim3(256), 0, s, x, ldx, (long)u.H * u.W, B, HW, C, nr, part,
-                           stat);
-      return;
-    }
+InStatsPlan in_stats_plan(int dt, int B, int H, int W, int C, int ldx, bool up2x, int nsem) {
+  InStatsPlan p;
+  if (dt != GHOST_F32 && !is16(dt)) return p;
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 16 || ldx % 8) return p;
+  if ((long)H * W * (up2x ? 4 : 1) > 0x7fffffffL || B > 65535) return p;
+  p.HW = (up2x ? 4 : 1) * H * W;
+  const int ncg = (C + 63) / 64;
+  static const int fuse_knob = GHOST_KNOB("GHOST_STATS_FUSE", 1);
+  const bool sem = fuse_knob && nsem > 0 && (long)B * ncg <= nsem;   // one counter per (sample, 64 channels)
+  if (up2x && in_stats_up2x_closed_form(dt, H, W, C, ldx)) {
+    // closed form over the source: (H / 4) * (W / 128) records <= the HW / 512 reserved
+    p.kernel = InStatsKernel::UpQuad;
+    p.chunk = 512;
+    p.nchunk = H * W / 512;   // workgroups of 512 source pixels
+    p.grid[0] = (unsigned)p.nchunk; p.grid[1] = (unsigned)(C / 64); p.grid[2] = (unsigned)B;
+    p.end = sem ? InStatsEnd::Fused : InStatsEnd::FinalKernel;
+  } else {
+    p.kernel = up2x ? InStatsKernel::PartialUp : InStatsKernel::Partial;
+    stats_geometry(B, p.HW, C, p.chunk, p.nchunk);
+    p.grid[0] = (unsigned)p.nchunk; p.grid[1] = (unsigned)ncg; p.grid[2] = (unsigned)B;
+    // one chunk: its workgroup finishes the statistics itself, with or without counters
+    p.end = p.nchunk == 1 ? InStatsEnd::Self : sem ? InStatsEnd::Fused : InStatsEnd::FinalKernel;
   }
-  if (up)
-    hipLaunchKernelGGL((in_stats_partial_kernel<T, true>), g1, dim3(256), 0, s, x, ldx, HW, C, chunk, nchunk, part, u,
-                       stat, sem);
-  else
-    hipLaunchKernelGGL((in_stats_partial_kernel<T, false>), g1, dim3(256), 0, s, x, ldx, HW, C, chunk, nchunk, part, u,
-                       stat, sem);
-  if (sem || nchunk == 1) return;   // the statistics are final (fused fix-up, or one chunk per workgroup)
-  const long bstride = up ? (long)u.H * u.W : HW;
-  hipLaunchKernelGGL(in_stats_final_kernel<T>, g2, dim3(256), 0, s, x, ldx, bstride, B, HW, C, nchunk, part, stat);
+  if (p.end == InStatsEnd::FinalKernel) p.final_grid = (unsigned)((B * C + 255) / 256);
+  if (p.end != InStatsEnd::Self) p.part_bytes = (size_t)B * p.nchunk * C * 2 * sizeof(float);
+  return p;
 }
 
-static int in_stats_any(int dt, const void* x, int ldx, int B, int HW, int C, float* stat, void* ws, size_t ws_bytes,
-                        const Up2xSrc* up, hipStream_t s, unsigned* sem, int nsem) {
-  if (C % 16 || ldx % 8 || (uintptr_t)x % 16) return -1;
-  if (!ws || ws_bytes < in_stats_workspace_bytes(B, HW, C)) return -1;
+int in_stats_plan_text(int dt, const InStatsPlan& p, char* buf, size_t cap) {
+  const char* k = p.kernel == InStatsKernel::Partial ? "partial" : p.kernel == InStatsKernel::PartialUp ? "partial_up" : "up_quad";
+  const char* e = p.end == InStatsEnd::Self ? "self" : p.end == InStatsEnd::Fused ? "fused" : "final_kernel";
+  return snprintf(buf, cap, "in_stats t=%s kernel=%s chunk=%d nchunk=%d end=%s",
+                  dt == GHOST_F32 ? "f32" : dt == GHOST_BF16 ? "bf16" : "f16", k, p.chunk, p.nchunk, e);
+}
+
+// launches what the plan says
+template <typename T>
+static void in_stats_launch(const InStatsPlan& p, const T* x, int ldx, int B, int C, float* stat, float* part,
+                            const Up2xSrc* up, hipStream_t s, unsigned* sem) {
+  const dim3 g1(p.grid[0], p.grid[1], p.grid[2]);
+  const Up2xSrc u = up ? *up : Up2xSrc{0, 0, 0.f, 0.f};
+  const int HW = p.HW;
+  if (p.end != InStatsEnd::Fused) sem = nullptr;
+  const long bstride = up ? (long)u.H * u.W : HW;
+  if (p.kernel == InStatsKernel::UpQuad) {
+    if constexpr (sizeof(T) == 2)
+      hipLaunchKernelGGL(in_stats_up_quad_kernel<T>, g1, dim3(256), 0, s, x, ldx, C, p.nchunk, part, u, stat, sem);
+  } else if (p.kernel == InStatsKernel::PartialUp) {
+    hipLaunchKernelGGL((in_stats_partial_kernel<T, true>), g1, dim3(256), 0, s, x, ldx, HW, C, p.chunk, p.nchunk, part, u,
+                       stat, sem);
+  } else {
+    hipLaunchKernelGGL((in_stats_partial_kernel<T, false>), g1, dim3(256), 0, s, x, ldx, HW, C, p.chunk, p.nchunk, part,
+                       u, stat, sem);
+  }
+  // Self / Fused: the statistics are final (one chunk per workgroup, or the fused fix-up)
+  if (p.end == InStatsEnd::FinalKernel)
+    hipLaunchKernelGGL(in_stats_final_kernel<T>, dim3(p.final_grid), dim3(256), 0, s, x, ldx, bstride, B, HW, C, p.nchunk,
+                       part, stat);
+}
+
+static int in_stats_any(int dt, const void* x, int ldx, int B, int H, int W, int C, float* stat, void* ws,
+                        size_t ws_bytes, const Up2xSrc* up, hipStream_t s, unsigned* sem, int nsem) {
+  if ((uintptr_t)x % 16) return -1;
+  const InStatsPlan p = in_stats_plan(dt, B, H, W, C, ldx, up != nullptr, sem ? nsem : 0);
+  if (p.kernel == InStatsKernel::None) return -1;
+  if (!ws || ws_bytes < in_stats_workspace_bytes(B, p.HW, C)) return -1;
   float* part = reinterpret_cast<float*>(ws);
-  static const int fuse_knob = GHOST_KNOB("GHOST_STATS_FUSE", 1);
-  if (!fuse_knob || (long)B * ((C + 63) / 64) > nsem) sem = nullptr;   // one counter per (sample, 64 channels)
   if (dt == GHOST_F32)
-    in_stats_launch((const float*)x, ldx, B, HW, C, stat, part, up, s, sem);
+    in_stats_launch(p, (const float*)x, ldx, B, C, stat, part, up, s, sem);
   else if (dt == GHOST_BF16)
-    in_stats_launch((const bf16*)x, ldx, B, HW, C, stat, part, up, s, sem);
-  else if (dt == GHOST_F16)
-    in_stats_launch((const _Float16*)x, ldx, B, HW, C, stat, part, up, s, sem);
+    in_stats_launch(p, (const bf16*)x, ldx, B, C, stat, part, up, s, sem);
   else
-    return -1;
+    in_stats_launch(p, (const _Float16*)x, ldx, B, C, stat, part, up, s, sem);
   return (int)hipGetLastError();
 }
 
 int in_stats(int dt, const void* x, int ldx, int B, int HW, int C, float* stat, void* ws, size_t ws_bytes,
              hipStream_t s, unsigned* sem, int nsem) {
-  return in_stats_any(dt, x, ldx, B, HW, C, stat, ws, ws_bytes, nullptr, s, sem, nsem);
+  return in_stats_any(dt, x, ldx, B, HW, 1, C, stat, ws, ws_bytes, nullptr, s, sem, nsem);
 }
 
 int in_stats_up2x(int dt, const void* x, int ldx, int B, int H, int W, int C, float* stat, void* ws, size_t ws_bytes,
                   hipStream_t s, unsigned* sem, int nsem) {
   const Up2xSrc u = up2x_src(H, W);
-  return in_stats_any(dt, x, ldx, B, 4 * H * W, C, stat, ws, ws_bytes, &u, s, sem, nsem);
+  return in_stats_any(dt, x, ldx, B, H, W, C, stat, ws, ws_bytes, &u, s, sem, nsem);
 }
 
 // ---------------------------------------------------------------------------

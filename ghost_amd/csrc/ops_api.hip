@@ -117,10 +117,95 @@ extern "C" int ghost_instnorm_stats_up2x_nhwc(int dtype, const void* x, int B, i
   return rc ? fail(rc, "in_stats_up2x failed") : 0;
 }
 
+static bool sem_ok(const unsigned* sem, int nsem);
+
+// Test support: the statistics as the runtimes call them (aei_runtime.hip run_stats / run_stats_up), with the arrival
+// counters of the fused final pass.  up2x = 1: x is the [B, H, W, C] source of the virtual upsample
+extern "C" int ghost_instnorm_stats_rt_nhwc(int dtype, const void* x, int B, int H, int W, int C, int ldx, int up2x,
+                                            float* stat, void* ws, int64_t ws_bytes, unsigned* sem, int nsem,
+                                            void* stream) {
+  if (!x || !stat || (up2x & ~1) || ws_bytes < 0) return fail(GHOST_EINVAL, "ghost_instnorm_stats_rt_nhwc: bad argument");
+  if (!sem_ok(sem, nsem)) return fail(GHOST_EINVAL, "ghost_instnorm_stats_rt_nhwc: sem / nsem must be (NULL, 0) or nsem > 0 words");
+  const InStatsPlan p = in_stats_plan(dtype, B, H, W, C, ldx, up2x != 0, nsem);
+  if (p.kernel == InStatsKernel::None || (uintptr_t)x % 16)
+    return fail(GHOST_EINVAL, "ghost_instnorm_stats_rt_nhwc: unsupported shape (C % 16, ldx % 8, a 16-byte aligned x)");
+  if (!ws || (size_t)ws_bytes < in_stats_workspace_bytes(B, p.HW, C))
+    return fail(GHOST_ENOWS, "ghost_instnorm_stats_rt_nhwc: workspace too small");
+  int rc = up2x ? in_stats_up2x(dtype, x, ldx, B, H, W, C, stat, ws, (size_t)ws_bytes, (hipStream_t)stream, sem, nsem)
+                : in_stats(dtype, x, ldx, B, H * W, C, stat, ws, (size_t)ws_bytes, (hipStream_t)stream, sem, nsem);
+  return rc ? fail(rc, "ghost_instnorm_stats_rt_nhwc failed") : 0;
+}
+
+extern "C" int64_t ghost_instnorm_plan(int dtype, int B, int H, int W, int C, int ldx, int up2x, int nsem,
+                                       int64_t* ws_bytes, char* buf, int64_t cap) {
+  if ((up2x & ~1) || nsem < 0 || cap < 0 || (cap > 0 && !buf)) return fail(GHOST_EINVAL, "instnorm_plan: bad argument");
+  const InStatsPlan p = in_stats_plan(dtype, B, H, W, C, ldx, up2x != 0, nsem);
+  if (p.kernel == InStatsKernel::None) return fail(GHOST_EINVAL, "instnorm_plan: in_stats rejects this shape");
+  char text[160];
+  const int n = in_stats_plan_text(dtype, p, text, sizeof(text));
+  if (ws_bytes) *ws_bytes = (int64_t)in_stats_workspace_bytes(B, p.HW, C);
+  if (cap > 0) snprintf(buf, (size_t)cap, "%s", text);
+  return (int64_t)n + 1;
+}
+
+// the arrival counters of a test-support entry: none (NULL, 0) or nsem > 0 words at sem
+static bool sem_ok(const unsigned* sem, int nsem) { return nsem >= 0 && (nsem > 0) == (sem != nullptr) && (uintptr_t)sem % 4 == 0; }
+
+// Test support: one convolution as the runtimes launch it (aei_runtime.hip run_conv, arc_runtime.hip's head): the
+// output type apart from the operand type, and the arrival counters of the split-K fix-up
+extern "C" int ghost_conv_rt_nhwc(int in_dtype, int out_dtype, int kind, const void* x, int B, int H, int W, int Cin,
+                                  int ldx, const void* w_packed, int Cout, int Npad, int Kpad, int kh, int kw,
+                                  int stride, int pad, const ghost_conv_epi* epi, void* y, int ldy, void* ws,
+                                  int64_t ws_bytes, unsigned* sem, int nsem, void* stream) {
+  if (!epi) return fail(GHOST_EINVAL, "ghost_conv_rt_nhwc: null epilogue");
+  if (kind != CONV_FWD && kind != CONV_T4S2) return fail(GHOST_EINVAL, "ghost_conv_rt_nhwc: kind must be 0 (FWD) or 1 (T4S2)");
+  if (epi->split_k < 0 || ws_bytes < 0) return fail(GHOST_EINVAL, "ghost_conv_rt_nhwc: split_k and ws_bytes must be >= 0");
+  if (!sem_ok(sem, nsem)) return fail(GHOST_EINVAL, "ghost_conv_rt_nhwc: sem / nsem must be (NULL, 0) or nsem > 0 words");
+  ConvDesc d = kind == CONV_T4S2
+                   ? conv_desc(in_dtype, out_dtype, x, B, H, W, Cin, ldx, w_packed, Cout, Npad, Kpad, CONV_T4S2, 1, 1, 1, 0, y, ldy)
+                   : conv_desc(in_dtype, out_dtype, x, B, H, W, Cin, ldx, w_packed, Cout, Npad, Kpad, CONV_FWD, kh, kw, stride,
+                               pad, y, ldy);
+  set_epi(d, epi);
+  d.sem = sem; d.nsem = nsem;
+  if (!conv_desc_ok(d)) return fail(GHOST_EINVAL, "ghost_conv_rt_nhwc: conv_launch rejects this descriptor");
+  // only the implicit GEMM has instances whose output type differs from the operand type, and not for every pair
+  if (conv_path(d) != ConvPath::Igemm ? in_dtype != out_dtype : igemm_plan(d).kernel == IgemmKernel::None)
+    return fail(GHOST_EINVAL, "ghost_conv_rt_nhwc: no kernel instance takes this descriptor (type pair, packing)");
+  return conv_op(d, ws, ws_bytes, stream, "ghost_conv_rt_nhwc");
+}
+
+static int aad_layer(int dtype, const void* h_in, int ldh, const void* z_attr, int lda, int B, int H, int W, int C, int Ca,
+                     const void* gbw_packed, int Npad, int Kpad, const float* gbb, const float* wh, const float* bh,
+                     const float* idgb, int id_ld, float slope, void* out, int ldo, void* ws, int64_t ws_bytes,
+                     int split_k, unsigned* sem, int nsem, void* stream);
+
 extern "C" int ghost_aad_layer_nhwc(int dtype, const void* h_in, int ldh, const void* z_attr, int lda, int B, int H,
                                     int W, int C, int Ca, const void* gbw_packed, int Npad, int Kpad, const float* gbb,
                                     const float* wh, const float* bh, const float* idgb, int id_ld, float slope,
                                     void* out, int ldo, void* ws, int64_t ws_bytes, void* stream) {
+  return aad_layer(dtype, h_in, ldh, z_attr, lda, B, H, W, C, Ca, gbw_packed, Npad, Kpad, gbb, wh, bh, idgb, id_ld, slope,
+                   out, ldo, ws, ws_bytes, 0, nullptr, 0, stream);
+}
+
+// Test support: ghost_aad_layer_nhwc as the runtime runs the layer at low resolution: a split of the GEMM's K, and
+// the arrival counters given to both the statistics and the GEMM (launches on one stream share the words)
+extern "C" int ghost_aad_layer_rt_nhwc(int dtype, const void* h_in, int ldh, const void* z_attr, int lda, int B, int H,
+                                       int W, int C, int Ca, const void* gbw_packed, int Npad, int Kpad,
+                                       const float* gbb, const float* wh, const float* bh, const float* idgb, int id_ld,
+                                       float slope, void* out, int ldo, void* ws, int64_t ws_bytes, int split_k,
+                                       unsigned* sem, int nsem, void* stream) {
+  if (split_k < 0 || ws_bytes < 0) return fail(GHOST_EINVAL, "ghost_aad_layer_rt_nhwc: split_k and ws_bytes must be >= 0");
+  if (!sem_ok(sem, nsem)) return fail(GHOST_EINVAL, "ghost_aad_layer_rt_nhwc: sem / nsem must be (NULL, 0) or nsem > 0 words");
+  if (!h_in || !z_attr || !gbw_packed || !gbb || !wh || !bh || !idgb || !out || B < 1 || H < 1 || W < 1 || C < 1 || Ca < 1)
+    return fail(GHOST_EINVAL, "ghost_aad_layer_rt_nhwc: null argument or empty shape");
+  return aad_layer(dtype, h_in, ldh, z_attr, lda, B, H, W, C, Ca, gbw_packed, Npad, Kpad, gbb, wh, bh, idgb, id_ld, slope,
+                   out, ldo, ws, ws_bytes, split_k, sem, nsem, stream);
+}
+
+static int aad_layer(int dtype, const void* h_in, int ldh, const void* z_attr, int lda, int B, int H, int W, int C, int Ca,
+                     const void* gbw_packed, int Npad, int Kpad, const float* gbb, const float* wh, const float* bh,
+                     const float* idgb, int id_ld, float slope, void* out, int ldo, void* ws, int64_t ws_bytes,
+                     int split_k, unsigned* sem, int nsem, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int HW = H * W;
   // workspace: stat [B][C][2] | mask [B*HW] | scratch (max of IN partials and split-K partials)
@@ -130,6 +215,7 @@ extern "C" int ghost_aad_layer_nhwc(int dtype, const void* h_in, int ldh, const 
                          out, ldo);
   d.shift = gbb; d.slope = slope; d.epi = EPI_AAD;
   d.hin = h_in; d.ldh = ldh; d.idgb = idgb; d.id_ld = id_ld; d.C_aad = C;
+  d.force_split = split_k; d.sem = sem; d.nsem = nsem;
   size_t sc = conv_workspace_bytes(d);
   const size_t st = in_stats_workspace_bytes(B, HW, C);
   if (st > sc) sc = st;
@@ -138,7 +224,7 @@ extern "C" int ghost_aad_layer_nhwc(int dtype, const void* h_in, int ldh, const 
   float* stat = (float*)base;
   float* mask = (float*)(base + stat_b);
   char* scratch = base + stat_b + mask_b;
-  int rc = in_stats(dtype, h_in, ldh, B, HW, C, stat, scratch, sc, s);
+  int rc = in_stats(dtype, h_in, ldh, B, HW, C, stat, scratch, sc, s, sem, nsem);
   if (rc) return fail(rc, "aad_layer: in_stats failed");
   // this entry takes gbw, not the w3 / b3 layout: Fused or Split
   if (aad_path(dtype, B, HW, C, Ca, lda, ldh, &ldo, 1, false) == AadPath::Fused) {

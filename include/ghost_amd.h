@@ -532,6 +532,36 @@ enum {
 int64_t ghost_conv_plan(int ti, int to, int kind, int B, int H, int W, int Cin, int ldx, int N, int Npad, int Kpad,
                         int kh, int kw, int stride, int pad, int ldy, int epi, int split_k, int min_wgs, int nsem,
                         int ncu, int flags, int64_t* ws_bytes, char* buf, int64_t cap);
+/* Test support, touches no device: the one line "in_stats t=<type> kernel=partial|partial_up|up_quad chunk=<pixels per
+ * record> nchunk=<records per sample> end=self|final_kernel|fused" of the plan that a statistics pass of this shape
+ * launches.  up2x = 0: an [B, H, W, C] tensor (only H * W matters); 1: the statistics of upsample2x of an [B, H, W, C]
+ * source.  nsem: arrival counters offered to the fused final pass (0: none).  *ws_bytes (may be NULL) receives the
+ * workspace the entries ask for.  The statistics are not in the plan log.  Returns as ghost_conv_plan does. */
+int64_t ghost_instnorm_plan(int dtype, int B, int H, int W, int C, int ldx, int up2x, int nsem, int64_t* ws_bytes,
+                            char* buf, int64_t cap);
+/* ---- Test support: single operators as the runtimes call them.  The last-arriver reductions (the split-K fix-up in
+ * the GEMM kernels, the fused final pass of the statistics) and the GEMMs whose output type differs from their
+ * operand type run only when the caller gives arrival counters or a second type, which only the network runtimes do;
+ * these entries take both as arguments, so that an op test can launch them alone.  sem / nsem: nsem > 0 32-bit
+ * counters, zero on entry and left zero, or (NULL, 0) for none; no global state.  GHOST_EINVAL, nothing launched: a
+ * bad argument, or a descriptor / type pair for which no kernel instance exists. */
+/* ghost_conv2d_ex_nhwc (kind 0) or ghost_conv_transpose4x4s2_nhwc (kind 1: kh, kw, stride, pad are ignored) with the
+ * operand type in_dtype, the output type out_dtype (f32 operands: any output; bf16 operands: bf16 or f32; f16
+ * operands: f16) and the counters of the split-K fix-up (one per tile and phase, else the reduction kernel runs) */
+int ghost_conv_rt_nhwc(int in_dtype, int out_dtype, int kind, const void* x, int B, int H, int W, int Cin, int ldx,
+                       const void* w_packed, int Cout, int Npad, int Kpad, int kh, int kw, int stride, int pad,
+                       const ghost_conv_epi* epi, void* y, int ldy, void* ws, int64_t ws_bytes, unsigned* sem, int nsem,
+                       void* stream);
+/* ghost_aad_layer_nhwc with a forced split of the GEMM's K (0: the heuristic's) and the counters, given to the
+ * statistics and to the GEMM */
+int ghost_aad_layer_rt_nhwc(int dtype, const void* h_in, int ldh, const void* z_attr, int lda, int B, int H, int W,
+                            int C, int Ca, const void* gbw_packed, int Npad, int Kpad, const float* gbb,
+                            const float* wh, const float* bh, const float* idgb, int id_ld, float slope, void* out,
+                            int ldo, void* ws, int64_t ws_bytes, int split_k, unsigned* sem, int nsem, void* stream);
+/* ghost_instnorm_stats_nhwc (up2x 0, HW = H * W) / ghost_instnorm_stats_up2x_nhwc (up2x 1) with the counters: one per
+ * (sample, 64-channel group), else the final kernel runs */
+int ghost_instnorm_stats_rt_nhwc(int dtype, const void* x, int B, int H, int W, int C, int ldx, int up2x, float* stat,
+                                 void* ws, int64_t ws_bytes, unsigned* sem, int nsem, void* stream);
 
 /* ---- SCRFD face detector (insightface scrfd_10g_bnkps) ----
  * The network, its letterbox and SCRFD.detect's post-processing for F device-resident frames of one size.  dtype:

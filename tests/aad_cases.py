@@ -244,8 +244,10 @@ def run_layers_v3(lib, case, slope):
     return outs, sigs
 
 
-def run_layer(lib, case, slope):
-    """ghost_aad_layer_nhwc (the module path: fused kernel or mask + GEMM epilogue) on a one-layer case."""
+def run_layer(lib, case, slope, rt=None):
+    """ghost_aad_layer_nhwc (the module path: fused kernel or mask + GEMM epilogue) on a one-layer case.
+    rt = dict(split_k, sem, nsem, ws): through ghost_aad_layer_rt_nhwc instead, as the runtime calls the layer (sem:
+    an int32 tensor of counters or None; ws: the workspace tensor to use, so that a second call can reuse it)."""
     from ghost_amd import _lib
     from ghost_amd.network.pack import pack_aad
     c, ca, H, W, B, dt = (case[k] for k in ("c", "ca", "H", "W", "B", "dt"))
@@ -259,12 +261,17 @@ def run_layer(lib, case, slope):
     hd = padded(case["hs"].reshape(B, -1, c), PAD, float("nan"))
     zad = padded(case["za"], PAD, float("nan"))
     out = torch.full((B, H * W, c + PAD), SENTINEL, dtype=dt, device=dev)
-    ws = torch.empty(256 << 20, dtype=torch.uint8, device=dev)
+    ws = rt["ws"] if rt else torch.empty(256 << 20, dtype=torch.uint8, device=dev)
     s = torch.cuda.current_stream().cuda_stream
-    sigs = logged_call(lambda: _lib.check(lib.ghost_aad_layer_nhwc(
-        _lib.gdtype(dt), hd.data_ptr(), c + PAD, zad.data_ptr(), ca + PAD, B, H, W, c, ca, pk["gbw"].data_ptr(),
-        pk["gbw"].shape[0], pk["gbw"].shape[1], pk["gbb"].data_ptr(), pk["wh"].data_ptr(), pk["bh"].data_ptr(),
-        idgb.data_ptr(), 2 * c, slope, out.data_ptr(), c + PAD, ws.data_ptr(), ws.numel(), s)))
+    args = (_lib.gdtype(dt), hd.data_ptr(), c + PAD, zad.data_ptr(), ca + PAD, B, H, W, c, ca, pk["gbw"].data_ptr(),
+            pk["gbw"].shape[0], pk["gbw"].shape[1], pk["gbb"].data_ptr(), pk["wh"].data_ptr(), pk["bh"].data_ptr(),
+            idgb.data_ptr(), 2 * c, slope, out.data_ptr(), c + PAD, ws.data_ptr(), ws.numel())
+    if rt:
+        sem = rt["sem"]
+        sigs = logged_call(lambda: _lib.check(lib.ghost_aad_layer_rt_nhwc(
+            *args, rt["split_k"], None if sem is None else sem.data_ptr(), rt["nsem"], s)))
+    else:
+        sigs = logged_call(lambda: _lib.check(lib.ghost_aad_layer_nhwc(*args, s)))
     return [out], sigs
 
 

@@ -58,6 +58,97 @@ def gemm_tokens(plan, t):
 
 
 # ----------------------------------------------------------------------------------------
+# The split-K fix-up (split_fixup, conv_igemm.hip) and the GEMMs whose output type differs from their operand type:
+# what only the runtimes select, through ghost_conv_rt_nhwc / ghost_aad_layer_rt_nhwc (tests/test_fused_reduce_ops.py
+# on the GPU, tests/test_conv_plan_cpu.py without one).  Each case: the smallest shape of its class, found by asking
+# ghost_conv_plan; the tokens of its GEMM line with the case's counters, and the reduction kernel that follows where
+# the plan does not fuse (`reduce`: also the line of the same call without counters).  The rule above holds.
+# ----------------------------------------------------------------------------------------
+NSEM = 4096             # the runtime's counter words (aei_runtime.hip kSemWords)
+T16 = ("bf16", "f16")
+T3 = T16 + ("f32",)
+_FIX_M = ("split=1", "fixup=std", "fixrows=M", "mtail=1")
+
+
+def _fix(name, tokens, B, H, W, cin, n, k=1, s=1, p=0, kind="fwd", split_k=0, types=("bf16", "f16"), nsem=NSEM,
+         reduce="splitk_reduce4", tokens_f32=None):
+    """tokens: the 16-bit GEMM line's (t=<type> is added for a glds line); tokens_f32: the fp32 line's, for a case
+    whose types hold f32.  A case with "fixup=none" among its tokens must run `reduce`; the others nothing."""
+    return dict(name=name, tokens=tuple(tokens), tokens_f32=tuple(tokens_f32 or ()), B=B, H=H, W=W, cin=cin, n=n, k=k, s=s,
+                p=p, kind=kind, split_k=split_k, types=tuple(types), nsem=nsem, reduce=reduce)
+
+
+_F32_M = ("igemm", "ti=f32", "to=f32", "64x128x32", "fast=1") + _FIX_M
+FIXUP_CASES = [
+    # glds 64x128, 15 rows of a 64-row tile: 4 x 15 x 128 x 4 = 30720 bytes of partials (test_igemm_thresholds' row)
+    _fix("glds64-rowsM", ("glds", "64x128", "stages=3", "kind=FWD", "ntail=0") + _FIX_M, 1, 3, 5, 512, 128, split_k=4,
+         types=T3, tokens_f32=_F32_M + ("kind=FWD",)),
+    # the deep ring: 4 x 16 x 128 x 4 = 32768, exactly the bound
+    _fix("deep-rowsM", ("glds", "128x128", "stages=8", "kind=FWD") + _FIX_M, 1, 4, 4, 1024, 256, split_k=4),
+    # the register-staged kernel: 256x32 tile, N tail inside the only column tile
+    _fix("igemm256x32", ("igemm", "256x32x32", "fast=1", "epi=SPLIT", "ntail=1") + _FIX_M, 1, 9, 5, 64, 24, 3, 1, 1,
+         split_k=3),
+    # two M tiles, the last of 67 rows: only the 256x16 tile holds a whole tile's partials of two splits in 32 KB
+    _fix("mtiles-tail", ("igemm", "256x16x32", "fast=1", "split=1", "fixup=std", "fixrows=BM", "mtail=1"), 1, 17, 19,
+         64, 16, 3, 1, 1, split_k=2),
+    # N tail: 72 and 2 columns in the last tile
+    _fix("ntail200", ("glds", "64x128", "ntail=1") + _FIX_M, 1, 3, 5, 64, 200, 3, 1, 1, split_k=2),
+    _fix("ntail130", ("glds", "64x128", "ntail=1") + _FIX_M, 1, 3, 5, 64, 130, 3, 1, 1, split_k=2, reduce="splitk_reduce"),
+    # nk = 27 in splits of 7, 7, 7, 6; nk = 5 in five splits of one K step (shorter than the ring's prologue)
+    _fix("ragged", ("glds", "64x128", "ragged=1", "short=0") + _FIX_M, 1, 3, 5, 96, 128, 3, 1, 1, split_k=4),
+    _fix("short", ("glds", "64x128", "ragged=0", "short=1", "ntail=1") + _FIX_M, 1, 3, 4, 160, 96, split_k=5),
+    # ConvT 4x4/s2: the four parity classes share the counter array; the heuristic's own split (production: B = 1, 2)
+    _fix("T4S2-deep", ("glds", "128x128", "stages=8", "kind=T4S2", "ntail=0") + _FIX_M, 2, 2, 2, 256, 256, kind="T",
+         types=T3, tokens_f32=_F32_M + ("kind=T4S2",)),
+    _fix("T4S2-ragged", ("glds", "64x128", "stages=3", "kind=T4S2", "ragged=1") + _FIX_M, 1, 2, 3, 544, 128, kind="T"),
+    # a counter per (phase, tile): 4 phases x 1 tile fuse with 4 words; with 3 the reduction kernel runs
+    _fix("T4S2-nsem4", ("glds", "64x128", "kind=T4S2") + _FIX_M, 1, 2, 3, 128, 128, kind="T", split_k=4, nsem=4),
+    _fix("T4S2-nsem3", ("glds", "64x128", "kind=T4S2", "split=1", "fixup=none"), 1, 2, 3, 128, 128, kind="T", split_k=4,
+         nsem=3),
+    _fix("nsem2", ("glds", "64x128", "kind=FWD") + _FIX_M, 1, 3, 5, 512, 256, split_k=4, nsem=2),
+    _fix("nsem1", ("glds", "64x128", "kind=FWD", "split=1", "fixup=none"), 1, 3, 5, 512, 256, split_k=4, nsem=1),
+]
+
+# fixup=aad through ghost_aad_layer_rt_nhwc: (name, tokens, tokens_f32, B, H, W, C, Ca, split_k, types).  The channel
+# strides are aad_cases.PAD wider than the channel counts.  The production form is the deep ring's (N = 2 C >= 256,
+# Ca >= 1024, the heuristic's four splits); no accepted C gives the deep ring a column tile beyond C_aad (it wants
+# N % 128 == 0), the register-staged 64x128 tile at C = 32 has one (columns 64 .. 127 of its only tile: channels
+# 32 .. 63).  The mask pass before the GEMM takes C / 8 (fp32: C / 4) a power of two only, so C = 80 is refused
+_AAD_M = ("epi=SPLIT", "split=1", "fixup=aad", "mtail=1", "fixrows=M")
+FIXUP_AAD_CASES = [
+    ("deep-B1", ("glds", "128x128", "stages=8", "ntail=0") + _AAD_M, _F32_M[:5] + _AAD_M, 1, 2, 2, 128, 1024, 0, T3),
+    ("deep-B3", ("glds", "128x128", "stages=8", "ntail=0") + _AAD_M, (), 3, 2, 2, 128, 1024, 0, T16),
+    ("deep-4x4", ("glds", "128x128", "stages=8", "ntail=0") + _AAD_M, (), 1, 4, 4, 128, 1024, 0, T16),
+    ("ntail-C32", ("igemm", "64x128x32", "fast=1", "ntail=1") + _AAD_M,
+     ("igemm", "ti=f32", "to=f32", "64x128x32", "fast=1", "ntail=1") + _AAD_M, 2, 3, 5, 32, 512, 0, T3),
+]
+
+# ghost_linear_f32 (unsplit, or split without counters: the reduction kernel) and the same GEMM through
+# ghost_conv_rt_nhwc with counters (the runtimes' "igemm ti=f32 ... fixup=std" line):
+# (name, B, K, N, split_k, counters, tokens without to=<type>, reduction kernel or None)
+LINEAR_LDY_PAD = 8
+LINEAR_CASES = [
+    ("tails-B1", 1, 100, 70, 0, 0, ("igemm", "ti=f32", "64x64x32", "fast=0", "epi=STD", "split=0", "ntail=1"), None),
+    ("tails-B3", 3, 100, 70, 0, 0, ("igemm", "ti=f32", "64x64x32", "fast=0", "epi=STD", "split=0", "ntail=1"), None),
+    ("split-nosem", 3, 512, 512, 0, 0, ("igemm", "ti=f32", "64x128x32", "fast=1", "split=1", "fixup=none"),
+     "splitk_reduce4"),
+    ("prod-B1", 1, 512, 512, 0, NSEM, ("igemm", "ti=f32", "64x128x32", "fast=1", "kind=FWD", "ntail=0") + _FIX_M, None),
+    ("prod-B3", 3, 512, 512, 0, NSEM, ("igemm", "ti=f32", "64x128x32", "fast=1", "kind=FWD", "ntail=0") + _FIX_M, None),
+    ("ntail130", 3, 1024, 130, 4, NSEM, ("igemm", "ti=f32", "64x128x32", "fast=1", "ntail=1") + _FIX_M, None),
+    ("gather-ragged", 3, 520, 200, 4, NSEM, ("igemm", "ti=f32", "64x64x32", "fast=0", "ragged=1", "ntail=1") + _FIX_M,
+     None),
+]
+
+# 16-bit operands with an fp32 output (the ArcFace head's form: a 7x7 valid conv on a 7x7 input, here 64 channels):
+# the GEMM writes partials even unsplit and splitk_reduce to=f32 applies the epilogue; counters never fuse it.
+# Only bf16 has instances (igemm_plan: f32_from16 wants ti == bf16): fp16 -> fp32 is refused, nothing launched.
+HEAD_CIN, HEAD_HW = 64, 7
+HEAD_TOKENS = ("igemm", "ti=bf16", "to=bf16", "64x128x32", "epi=SPLIT", "fixup=none")
+HEAD_REDUCE = "splitk_reduce to=f32 epi=STD from=bf16"
+HEAD_CASES = [(n, B, nsem) for n in (512, 200) for B in (1, 3) for nsem in (0, NSEM)]
+
+
+# ----------------------------------------------------------------------------------------
 # The convolution families off the implicit GEMM: halo, halo_pp, convT_halo, s2_patch, first, stem3x3.  One entry per
 # variant, each at the smallest shape that selects it (halo_plan wants 64 work items, convT_halo 128 workgroups,
 # s2_patch 32), with the tokens its plan-log line must hold.  tests/test_conv_ops.py runs them on the GPU against a
@@ -89,7 +180,6 @@ def mode_flags(mode):
 
 
 LDY_PAD = 8
-T16 = ("bf16", "f16")
 
 
 def _case(tokens, B, H, W, cin, n, mode="bn", k=3, s=1, p=1, kind="fwd", ldx=None, ldy=None, types=T16, stats=False):

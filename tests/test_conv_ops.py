@@ -1,7 +1,8 @@
 """Op tests of the convolution kernels off the implicit GEMM (MI355X): halo, halo_pp, convT_halo, s2_patch, first and
 stem3x3, every production variant pinned by its plan-log line, against a float64 reference of the same operation,
 per element.  The cases are conv_cases.FAMILY_CASES (tests/test_conv_plan_cpu.py checks the same signatures without a
-GPU); the implicit GEMM's own edge classes are gated in tests/test_gpu_parity.py.
+GPU); the implicit GEMM's own edge classes are gated in tests/test_gpu_parity.py, its split-K fix-up (arrival counters)
+and its mixed-type instances in tests/test_fused_reduce_ops.py.
 
   reference  F.conv2d / F.conv_transpose2d and the epilogue of include/ghost_amd.h (ghost_conv_epi) in float64 on the
              CPU; x, w and the residual pre-rounded to the storage type, scale, shift, PReLU, scale2 and shift2 the

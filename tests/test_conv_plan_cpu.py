@@ -335,3 +335,131 @@ def test_workspace(lib):
     lines, ws = plan(lib, BF16, 1, 256, 256, 3, 32, 4, 2, 1, ldx=4)
     assert lines == ["first mfma t=bf16 chunktail=0"] and ws == 32 * 48 * 4
     assert plan(lib, F32, 1, 256, 256, 3, 32, 4, 2, 1, ldx=3) == (["first scalar t=f32 mtail=0"], 32 * 48 * 4)
+
+
+# ----------------------------------------------------------------------------------------
+# what only the runtimes select (tests/test_fused_reduce_ops.py on the GPU): the split-K fix-up with arrival counters,
+# the GEMMs whose output type differs from their operand type
+# ----------------------------------------------------------------------------------------
+DT = {"bf16": BF16, "f16": F16, "f32": F32}
+
+
+def fixup_plan(lib, c, t, nsem):
+    return plan(lib, DT[t], c["B"], c["H"], c["W"], c["cin"], c["n"], c["k"], c["s"], c["p"],
+                kind=T4S2 if c["kind"] == "T" else FWD, ldy=c["n"] + K.IGEMM_LDY_PAD, split_k=c["split_k"], nsem=nsem)
+
+
+def fixup_tokens(c, t):
+    return c["tokens_f32"] if t == "f32" else K.gemm_tokens(c["tokens"], t)
+
+
+@pytest.mark.parametrize("c,t", [pytest.param(c, t, id=f"{c['name']}-{t}") for c in K.FIXUP_CASES for t in c["types"]])
+def test_fixup_case_signatures(lib, c, t):
+    """With the case's counters: its GEMM line, and no reduction exactly when the line says fixup=std.  Without
+    counters the same GEMM but fixup=none, followed by the case's reduction kernel; the workspace is the same."""
+    lines, ws = fixup_plan(lib, c, t, c["nsem"])
+    assert has(lines[0], *fixup_tokens(c, t)), (fixup_tokens(c, t), lines)
+    fused = "fixup=none" not in c["tokens"]
+    assert has(lines[0], "fixup=std" if fused else "fixup=none")
+    assert [l.split()[0] for l in lines[1:]] == ([] if fused else [c["reduce"]]), lines
+    plain, ws0 = fixup_plan(lib, c, t, 0)
+    assert plain[0] == lines[0].replace("fixup=std", "fixup=none").replace(" fixrows=M", "").replace(" fixrows=BM", "")
+    assert plain[1] == f"{c['reduce']} to={t} epi=STD" and len(plain) == 2 and ws0 == ws > 0
+
+
+def test_fixup_counter_boundaries(lib):
+    """A counter per (phase, tile): the cases at nsem == tiles fuse, their twins at nsem - 1 do not; both otherwise
+    the same descriptor."""
+    by = {c["name"]: c for c in K.FIXUP_CASES}
+    for hi, lo in (("T4S2-nsem4", "T4S2-nsem3"), ("nsem2", "nsem1")):
+        a, b = by[hi], by[lo]
+        assert {k: v for k, v in a.items() if k not in ("name", "tokens", "nsem")} == \
+               {k: v for k, v in b.items() if k not in ("name", "tokens", "nsem")}
+        assert a["nsem"] == b["nsem"] + 1
+        for t in a["types"]:
+            assert has(fixup_plan(lib, a, t, a["nsem"])[0][0], "fixup=std")
+            assert has(fixup_plan(lib, a, t, a["nsem"] - 1)[0][0], "fixup=none")
+            assert has(fixup_plan(lib, a, t, a["nsem"] + 1)[0][0], "fixup=std")
+
+
+@pytest.mark.parametrize("name,tokens,tokens_f32,B,H,W,c,ca,split_k,types", K.FIXUP_AAD_CASES,
+                         ids=[r[0] for r in K.FIXUP_AAD_CASES])
+def test_fixup_aad_case_signatures(lib, name, tokens, tokens_f32, B, H, W, c, ca, split_k, types):
+    """The GEMM of ghost_aad_layer_rt_nhwc on aad_cases' strides (channel counts + 8)."""
+    for t in types:
+        lines, _ = plan(lib, DT[t], B, H, W, ca, 2 * c, 1, 1, 0, ldx=ca + 8, ldy=c + 8, epi=1, split_k=split_k, nsem=K.NSEM)
+        want = tokens_f32 if t == "f32" else K.gemm_tokens(tokens, t)
+        assert len(lines) == 1 and has(lines[0], *want), (want, lines)
+        plain, _ = plan(lib, DT[t], B, H, W, ca, 2 * c, 1, 1, 0, ldx=ca + 8, ldy=c + 8, epi=1, split_k=split_k)
+        assert has(plain[0], "fixup=none") and plain[1] == f"splitk_reduce4 to={t} epi=AAD", plain
+
+
+@pytest.mark.parametrize("to", ["f32", "bf16", "f16"])
+@pytest.mark.parametrize("name,B,Kc,N,split_k,nsem,tokens,reduce", K.LINEAR_CASES, ids=[r[0] for r in K.LINEAR_CASES])
+def test_linear_case_signatures(lib, to, name, B, Kc, N, split_k, nsem, tokens, reduce):
+    lines, _ = plan(lib, F32, B, 1, 1, Kc, N, 1, 1, 0, to=DT[to], ldy=N + K.LINEAR_LDY_PAD, split_k=split_k, nsem=nsem)
+    assert has(lines[0], "to=" + to, *tokens), (tokens, lines)
+    assert lines[1:] == ([f"{reduce} to={to} epi=STD"] if reduce else []), lines
+
+
+@pytest.mark.parametrize("n,B,nsem", K.HEAD_CASES)
+def test_head_case_signatures(lib, n, B, nsem):
+    """16-bit operands, fp32 output: partials and splitk_reduce to=f32 with or without counters; bf16 only."""
+    a = (B, K.HEAD_HW, K.HEAD_HW, K.HEAD_CIN, n, K.HEAD_HW, 1, 0)
+    lines, ws = plan(lib, BF16, *a, to=F32, ldy=n + K.IGEMM_LDY_PAD, nsem=nsem)
+    assert has(lines[0], *K.HEAD_TOKENS) and has(lines[0], "ntail=%d" % (n % 128 != 0)), lines
+    assert lines[1:] == [K.HEAD_REDUCE] and ws > 0, lines
+    assert plan(lib, F16, *a, to=F32, nsem=nsem)[0] is None
+
+
+def test_design_fused_signatures_are_covered_by_the_cases(lib):
+    """Every fixup=std / fixup=aad line of DESIGN.md section 2 is the plan of a case above (what the closing test of
+    tests/test_fused_reduce_ops.py asks of the plan log on the GPU)."""
+    with open(os.path.join(REPO, "DESIGN.md")) as f:
+        want = set(re.findall(r"\| `([^`]*fixup=(?:std|aad)[^`]*)` \|", f.read()))
+    assert len(want) >= 10, want
+    got = set()
+    for c in K.FIXUP_CASES:
+        got.update(fixup_plan(lib, c, t, c["nsem"])[0][0] for t in c["types"])
+    for _, _, _, B, H, W, c, ca, split_k, types in K.FIXUP_AAD_CASES:
+        got.update(plan(lib, DT[t], B, H, W, ca, 2 * c, 1, 1, 0, ldx=ca + 8, ldy=c + 8, epi=1, split_k=split_k,
+                        nsem=K.NSEM)[0][0] for t in types)
+    for _, B, Kc, N, split_k, nsem, _, _ in K.LINEAR_CASES:
+        got.update(plan(lib, F32, B, 1, 1, Kc, N, 1, 1, 0, to=DT[to], split_k=split_k, nsem=nsem)[0][0] for to in DT)
+    assert want <= got, sorted(want - got)
+
+
+def test_rt_entries_reject_bad_arguments_without_launching(lib):
+    """ghost_conv_rt_nhwc and ghost_aad_layer_rt_nhwc refuse before any launch: nothing reaches the plan log (host
+    memory stands for every pointer: there is no device here)."""
+    mem = (C.c_char * 4096)()
+    a = C.addressof(mem)
+    a += -a % 16
+    e = _lib.ConvEpi()
+    e.slope = 1.0
+
+    def conv(ti=BF16, to=BF16, kind=FWD, x=a, epi=C.byref(e), npad=128, kpad=512, ws_bytes=1 << 20, sem=None, nsem=0):
+        return lib.ghost_conv_rt_nhwc(ti, to, kind, x, 1, 3, 5, 512, 512, a, 128, npad, kpad, 1, 1, 1, 0, epi, a, 128, a,
+                                      ws_bytes, sem, nsem, None)
+
+    def aad(split_k=0, sem=None, nsem=0, h=a, ws_bytes=1 << 20):
+        return lib.ghost_aad_layer_rt_nhwc(BF16, h, 128, a, 1024, 1, 2, 2, 128, 1024, a, 256, 1024, a, a, a, a, 256, 1.0,
+                                           a, 128, a, ws_bytes, split_k, sem, nsem, None)
+    _lib.plan_log(True)
+    try:
+        assert conv(epi=None) == -1 and conv(kind=2) == -1 and conv(x=None) == -1 and conv(ws_bytes=-1) == -1
+        assert conv(sem=None, nsem=4) == -1 and conv(sem=a, nsem=0) == -1 and conv(sem=a, nsem=-1) == -1
+        assert conv(npad=64) == -1 and conv(kpad=500) == -1 and conv(kpad=256) == -1      # packing the tiles overrun
+        # type pairs without an instance: fp16 -> fp32, 16-bit -> the other 16-bit type, bf16 -> fp32 with a residual
+        assert conv(ti=F16, to=F32) == -1 and conv(ti=BF16, to=F16) == -1 and conv(ti=F16, to=BF16) == -1
+        e.res, e.ldres = a, 128
+        assert conv(ti=BF16, to=F32) == -1
+        e.res, e.split_k = None, -1
+        assert conv() == -1
+        e.split_k = 0
+        assert b"ghost_conv_rt_nhwc" in lib.ghost_last_error()
+        assert aad(split_k=-1) == -1 and aad(sem=None, nsem=1) == -1 and aad(sem=a, nsem=0) == -1 and aad(h=None) == -1
+        assert aad(ws_bytes=-1) == -1 and aad(ws_bytes=64) == -3
+    finally:
+        _lib.plan_log(False)
+    assert _lib.plan_log_read() == []

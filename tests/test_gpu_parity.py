@@ -11,6 +11,8 @@ Gates
   bf16-storage-emulating oracle (oracle/aei_ref.aei_forward_bf16_storage: the same stored
   roundings, fp32 in between) by more than 25 % in mean and 99.9th percentile; the tight
   per-stage gates against that oracle are in tests/test_bf16_parity.py.
+* what only the runtimes select (the split-K fix-up and the fused statistics pass with arrival counters, GEMMs whose
+  output type differs from their operands'): op tests in tests/test_fused_reduce_ops.py.
 """
 import os
 
