@@ -18,14 +18,19 @@
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes as C
 import operator
 import types
 import weakref
 from typing import Callable
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.modules.module as _tmod
+
+from . import _lib
 
 _VERSION = operator.attrgetter("_version")
 _OWNER = "_ghost_pack_owner"
@@ -144,3 +149,96 @@ class WorkspaceCache:
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.ws[key] = ws
         return ws
+
+
+class NativeRuntime:
+    """A native handle (``ghost_<prefix>_create`` .. ``_destroy``) with every packed tensor bound to its slot, for
+    one (device, compute dtype); ``slots`` keeps the packed tensors alive.  ``what`` opens the error messages
+    ("landmark ", or "" for the flagship)."""
+
+    def __init__(self, prefix: str, what: str, dtype, slots, *create_args):
+        self.lib = _lib.load()
+        self.prefix, self.what, self.dtype = prefix, what, dtype
+        self.h = None
+        h = C.c_void_p()
+        _lib.check(self._fn("create")(*create_args, C.byref(h)), f"ghost_{prefix}_create")
+        self.h = h
+        self.slots = slots
+        self.ws = WorkspaceCache()   # key (ends in the stream) -> workspace (stream-ordered reuse)
+        for name, t in slots.items():
+            _lib.check(self._fn("bind")(h, name.encode(), t.data_ptr(), t.numel()), f"bind {name}")
+        if self._fn("missing")(h) != 0:
+            _lib.check(-2, f"{what}weights incomplete")
+
+    def _fn(self, name: str):
+        return getattr(self.lib, f"ghost_{self.prefix}_{name}")
+
+    def workspace_for(self, nbytes_fn, key, dev: torch.device) -> torch.Tensor:
+        """The cached workspace for ``key``, sized by ``nbytes_fn()`` (a negative size is the native error)."""
+
+        def nbytes():
+            n = nbytes_fn()
+            if n < 0:
+                _lib.check(int(n), f"{self.what}workspace sizing")
+            return n
+        return self.ws.get(key, nbytes, dev)
+
+    def batch_workspace(self, N: int, dev: torch.device) -> torch.Tensor:
+        """One workspace per (N, current stream of ``dev``), sized by ``ghost_<prefix>_workspace_bytes(h, N)``."""
+        return self.workspace_for(lambda: self._fn("workspace_bytes")(self.h, N), (N, _lib.stream_ptr(dev)), dev)
+
+    def _set_taps(self, ptrs):
+        n = len(ptrs) if ptrs else 0
+        return self._fn("set_taps")(self.h, (C.c_void_p * n)(*ptrs) if n else None, n)
+
+    @contextlib.contextmanager
+    def taps(self, ptrs, what: str):
+        """Diagnostic tap pointers set for the calls inside the block and cleared after it, whatever happens."""
+        _lib.check(self._set_taps(ptrs), what)
+        try:
+            yield
+        finally:
+            self._set_taps(None)
+
+    def __del__(self):
+        try:
+            if self.h:
+                self._fn("destroy")(self.h)
+        except Exception:
+            pass
+
+
+def to_tensor(v) -> torch.Tensor:
+    """A checkpoint value (torch tensor, numpy array or anything with ``.asnumpy()``) as a tensor of its own shape."""
+    if torch.is_tensor(v):
+        return v.detach()
+    if hasattr(v, "asnumpy"):
+        v = v.asnumpy()
+    a = np.asarray(v)      # (np.ascontiguousarray would turn a 0-d array into [1])
+    return torch.from_numpy(a if a.flags.c_contiguous else np.ascontiguousarray(a))
+
+
+def load_named(own: dict, want: dict, given, model: str) -> None:
+    """Copy ``given`` ({name: value}) into the tensors ``own``: exactly ``want``'s names ({name: shape}) and shapes."""
+    missing = sorted(set(want) - set(given))
+    extra = sorted(set(given) - set(want))
+    if missing or extra:
+        raise KeyError(f"ghost_amd: {model} parameters do not match: missing {missing}, unexpected {extra}")
+    with torch.no_grad():
+        for n, shape in want.items():
+            t = to_tensor(given[n])
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"ghost_amd: {n} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+            own[n].copy_(t.to(own[n].device, own[n].dtype))
+
+
+def u8_rows(x: torch.Tensor, single_dense: bool = True):
+    """uint8 [N,H,W,3] whose rows are contiguous, the batch possibly strided -> (tensor, batch stride in bytes),
+    copying only when a sample itself is strided.  ``single_dense``: a batch of one is passed whole, with H*W*3
+    as its stride."""
+    H, W = x.shape[1], x.shape[2]
+    if single_dense and x.shape[0] == 1:
+        return (x if x.is_contiguous() else x.contiguous()), H * W * 3
+    if x.shape[0] and x[0].stride() != (W * 3, 3, 1):
+        x = x.contiguous()
+    return x, x.stride(0)

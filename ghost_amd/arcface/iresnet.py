@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .._packed import PackedModule, WorkspaceCache
+from .._packed import NativeRuntime, PackedModule, u8_rows
 
 WIDTHS = (64, 128, 256, 512)
 
@@ -59,27 +59,9 @@ class IBasicBlock(nn.Module):
         raise NotImplementedError("ghost_amd: IBasicBlock runs inside IResNet.forward on the MI355X path")
 
 
-class _Runtime:
+class _Runtime(NativeRuntime):
     def __init__(self, layers, nf, dtype, slots):
-        self.lib = _lib.load()
-        self.dtype = dtype
-        h = C.c_void_p()
-        arr = (C.c_int * 4)(*layers)
-        _lib.check(self.lib.ghost_arc_create(arr, nf, _lib.gdtype(dtype), C.byref(h)), "ghost_arc_create")
-        self.h = h
-        self.slots = slots
-        self.ws = WorkspaceCache()   # (N, stream) -> workspace
-        for name, t in slots.items():
-            _lib.check(self.lib.ghost_arc_bind(h, name.encode(), t.data_ptr(), t.numel()), f"bind {name}")
-        if self.lib.ghost_arc_missing(h) != 0:
-            _lib.check(-2, "ArcFace weights incomplete")
-
-    def __del__(self):
-        try:
-            if self.h:
-                self.lib.ghost_arc_destroy(self.h)
-        except Exception:
-            pass
+        super().__init__("arc", "ArcFace ", dtype, slots, (C.c_int * 4)(*layers), nf, _lib.gdtype(dtype))
 
 
 class IResNet(PackedModule):
@@ -143,14 +125,6 @@ class IResNet(PackedModule):
         return self._cached_runtime(device, dt, lambda sd: _Runtime(self.layers_cfg, self.num_features, dt,
                                                                      pack_iresnet(sd, self.layers_cfg, dt)))
 
-    def _workspace(self, rt, N, dev):
-        def nbytes():
-            n = rt.lib.ghost_arc_workspace_bytes(rt.h, N)
-            if n < 0:
-                _lib.check(int(n), "ArcFace workspace sizing")
-            return n
-        return rt.ws.get((N, _lib.stream_ptr(dev)), nbytes, dev)
-
     # -- execution -------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, x):
@@ -163,7 +137,7 @@ class IResNet(PackedModule):
         rt = self._runtime(x.device)
         N = x.shape[0]
         emb = torch.empty(N, self.num_features, dtype=torch.float32, device=x.device)
-        ws = self._workspace(rt, N, x.device)
+        ws = rt.batch_workspace(N, x.device)
         st = (C.c_int64 * 4)(*x.stride())
         _lib.check(rt.lib.ghost_arc_forward(rt.h, x.data_ptr(), _lib.gdtype(x.dtype), st, N, emb.data_ptr(),
                                             ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)), "IResNet.forward")
@@ -183,12 +157,8 @@ class IResNet(PackedModule):
                 shapes.append((shapes[-1][0] // (2 if b == 0 else 1), planes))
         bufs = [(torch.empty(N, h, h, c, dtype=rt.dtype, device=dev), torch.empty(N, h, h, c, dtype=rt.dtype, device=dev))
                 for h, c in shapes]
-        ptrs = (C.c_void_p * (2 * len(bufs)))(*[t.data_ptr() for pair in bufs for t in pair])
-        _lib.check(rt.lib.ghost_arc_set_taps(rt.h, ptrs, 2 * len(bufs)), "arc taps")
-        try:
+        with rt.taps([t.data_ptr() for pair in bufs for t in pair], "arc taps"):
             emb = self.forward(x)
-        finally:
-            rt.lib.ghost_arc_set_taps(rt.h, None, 0)
         return emb, [(a.permute(0, 3, 1, 2), b.permute(0, 3, 1, 2)) for a, b in bufs]
 
     @torch.no_grad()
@@ -198,13 +168,12 @@ class IResNet(PackedModule):
         _lib.require_gpu(crops, "IResNet.embed_u8")
         if crops.dtype != torch.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
             raise RuntimeError("ghost_amd: crops must be uint8 [N,H,W,3]")
-        if crops[0].stride() != (crops.shape[2] * 3, 3, 1):
-            crops = crops.contiguous()
+        crops, bs = u8_rows(crops, single_dense=False)
         rt = self._runtime(crops.device)
         N, H, W = crops.shape[:3]
         emb = torch.empty(N, self.num_features, dtype=torch.float32, device=crops.device)
-        ws = self._workspace(rt, N, crops.device)
-        _lib.check(rt.lib.ghost_arc_embed_u8(rt.h, crops.data_ptr(), crops.stride(0), N, H, W, emb.data_ptr(),
+        ws = rt.batch_workspace(N, crops.device)
+        _lib.check(rt.lib.ghost_arc_embed_u8(rt.h, crops.data_ptr(), bs, N, H, W, emb.data_ptr(),
                                              ws.data_ptr(), ws.numel(), _lib.stream_ptr(crops.device)),
                    "IResNet.embed_u8")
         return emb

@@ -1086,15 +1086,14 @@ extern "C" int ghost_aei_create(const char* backbone, int num_blocks, int c_id, 
     return fail(GHOST_EINVAL, "backbone must be 'unet', 'linknet' or 'resnet' (got " + bb + ")");
   if (num_blocks < 1 || num_blocks > 8) return fail(GHOST_EINVAL, "num_blocks out of range");
   if (c_id <= 0 || c_id % 32) return fail(GHOST_EINVAL, "c_id must be a positive multiple of 32");
-  if (dtype != GHOST_F32 && dtype != GHOST_BF16 && dtype != GHOST_F16)
-    return fail(GHOST_EINVAL, "dtype must be f32, bf16 or f16");
+  if (!storage_esz(dtype)) return fail(GHOST_EINVAL, "dtype must be f32, bf16 or f16");
   ghost_aei* h = new ghost_aei();
   h->linknet = bb == "linknet";
   h->resnet = bb == "resnet";
   h->nb = num_blocks;
   h->c_id = c_id;
   h->dt = dtype;
-  h->esz = dtype == GHOST_F32 ? 4 : 2;
+  h->esz = storage_esz(dtype);
   declare_slots(h);
   *out = h;
   return 0;

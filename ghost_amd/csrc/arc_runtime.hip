@@ -31,23 +31,19 @@ using namespace ghost;
 
 static int arc_fail(int rc, const std::string& msg) { return ghost::set_last_error(rc, msg); }
 
-struct ghost_arc {
+// diagnostic taps (ghost_arc_set_taps): stage i (0 = stem, i = block i) copies its stored residual
+// stream X into taps[2i] and the next BatchNorm's second output XB into taps[2i+1] when non-null
+struct ghost_arc : Handle {
+  static constexpr int kTaps = 0;
+  static constexpr bool kAligned16 = false;
   int layers[4] = {3, 13, 30, 3};
   int nf = 512;
-  int dt = GHOST_F32, esz = 4;
-  Slots slots;
-  // diagnostic taps (ghost_arc_set_taps): stage i (0 = stem, i = block i) copies its stored residual
-  // stream X into taps[2i] and the next BatchNorm's second output XB into taps[2i+1] when non-null
-  std::vector<void*> taps;
 };
 
 namespace {
 
 const int kWidths[4] = {64, 128, 256, 512};
-struct ArcCtx : PlanCtx {
-  ghost_arc* h = nullptr;
-  const void* W(const std::string& name) { return PlanCtx::W(h->slots, name); }
-};
+typedef HandleCtx<ghost_arc> ArcCtx;
 
 static int arc_min_wgs() {
   static const int v = GHOST_KNOB("GHOST_ARC_MINWG", 0);
@@ -100,11 +96,9 @@ void arc_plan(ArcCtx& c, const void* xin, int N, float* emb) {
   };
   // per-stage tap copies (parity bisection: the oracle recomputes each stage from the GPU's own inputs)
   auto tap = [&](size_t stage, const void* x, const void* xb, size_t bytes) {
-    if (c.dry || !c.ok() || 2 * stage + 1 >= h->taps.size()) return;
-    if (h->taps[2 * stage])
-      c.check((int)hipMemcpyAsync(h->taps[2 * stage], x, bytes, hipMemcpyDeviceToDevice, c.s), "tap copy");
-    if (h->taps[2 * stage + 1])
-      c.check((int)hipMemcpyAsync(h->taps[2 * stage + 1], xb, bytes, hipMemcpyDeviceToDevice, c.s), "tap copy");
+    if (2 * stage + 1 >= h->taps.size()) return;   // a stage is tapped as a pair or not at all
+    c.tap(2 * stage, x, bytes);
+    c.tap(2 * stage + 1, xb, bytes);
   };
   // stem: conv1 3x3 3->64 + bn1 + prelu  (X), bn1 of the first block (XB)
   conv_bn(c, "stem.w", "stem.bn", xin, 4, N, 112, 3, 64, 3, 1, X[0], "stem.prelu", nullptr, XB[0], next_bn(0));
@@ -154,16 +148,14 @@ void declare(ghost_arc* h) {
   add("fc.w"); add("fc.scale"); add("fc.shift");
 }
 
-int64_t arc_bytes(ghost_arc* h, int N, size_t* scratch) {
-  ArcCtx c{};
-  c.h = h; c.dry = true;
-  void* xin = c.alloc((size_t)N * 112 * 112 * 4 * h->esz);
-  float* emb = (float*)uintptr_t(0x30000000);
-  arc_plan(c, xin, N, emb);
-  if (!c.ok()) return c.rc;
-  c.alloc(256);   // u8 max flag
-  *scratch = c.scratch_need;
-  return (int64_t)(align_up(c.off) + c.scratch_need + 256);
+void* arc_xin(ArcCtx& c, int N) { return c.alloc((size_t)N * 112 * 112 * 4 * c.h->esz); }
+
+// the workspace: xin, the plan's buffers, the 256-byte region of the u8 max flag, the scratch
+PlanSize arc_bytes(ghost_arc* h, int N) {
+  return size_plan<ArcCtx>(h, [&](ArcCtx& c) {
+    arc_plan(c, arc_xin(c, N), N, (float*)uintptr_t(0x30000000));
+    c.alloc(256);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -287,49 +279,31 @@ __global__ void __launch_bounds__(256) arc_match_kernel(const float* __restrict_
 
 int run_arc(ghost_arc* h, int N, const void* xt, int xt_dtype, const int64_t* st, const uint8_t* crops,
             int64_t crop_bs, int Hs, int Ws, float* emb, void* ws, int64_t ws_bytes, void* stream) {
-  if (!h) return arc_fail(GHOST_EINVAL, "null handle");
-  if (N <= 0 || N > 65535) return arc_fail(GHOST_EINVAL, "batch must be in 1..65535");
+  if (const int rc = check_batch(h, N, 1, 65535)) return rc;
   if (count_missing(h->slots)) return GHOST_ENOTREADY;
-  size_t scratch = 0;
-  const int64_t need = arc_bytes(h, N, &scratch);
-  if (need < 0) return arc_fail((int)need, "plan sizing failed");
-  if (!ws || ws_bytes < need) return arc_fail(GHOST_ENOWS, "workspace too small: need " + std::to_string(need));
-  ArcCtx c{};
-  c.h = h; c.dry = false;
-  c.base = align_up(ws);
-  c.s = (hipStream_t)stream;
-  void* xin = c.alloc((size_t)N * 112 * 112 * 4 * h->esz);
-  // same allocation order as arc_bytes: the plan's buffers, then the flag, then the scratch
-  ArcCtx probe{};
-  probe.h = h; probe.dry = true;
-  probe.alloc((size_t)N * 112 * 112 * 4 * h->esz);
-  arc_plan(probe, probe.base, N, emb);
-  const size_t plan_end = align_up(probe.off);
-  int* flag = (int*)(c.base + plan_end);
-  c.scratch = c.base + plan_end + 256;
-  c.scratch_cap = scratch;
-  if (crops) {
-    if (hipMemsetAsync(flag, 0, sizeof(int), c.s) != hipSuccess) return arc_fail(GHOST_EINVAL, "memset failed");
-    const int per = Hs * Ws * 3;
-    hipLaunchKernelGGL(u8_max_kernel, dim3(8, (unsigned)N), dim3(256), 0, c.s, crops, (long)crop_bs, per, flag);
-    const float sh = (float)(Hs - 1) / (float)(112 - 1), sw = (float)(Ws - 1) / (float)(112 - 1);
-    const long P = (long)N * 112 * 112;
-    dim3 grid((unsigned)((P + 255) / 256));
-    if (h->dt == GHOST_F32)
-      hipLaunchKernelGGL(arc_prep_kernel<float>, grid, dim3(256), 0, c.s, crops, (long)crop_bs, N, Hs, Ws, 112, 112,
-                         sh, sw, flag, (float*)xin);
-    else
-      hipLaunchKernelGGL(arc_prep_kernel<bf16>, grid, dim3(256), 0, c.s, crops, (long)crop_bs, N, Hs, Ws, 112, 112,
-                         sh, sw, flag, (bf16*)xin);
-    c.check((int)hipGetLastError(), "arc_prep");
-  } else {
-    c.check(input_to_nhwc(xt_dtype, xt, st, N, 3, 112, 112, h->dt, xin, c.s, 4), "input_to_nhwc");
-  }
-  arc_plan(c, xin, N, emb);
-  if (!c.ok())
-    return arc_fail(c.rc, "ArcFace forward failed at " + c.where +
-                              (c.rc > 0 ? std::string(": ") + hipGetErrorString((hipError_t)c.rc) : std::string()));
-  return 0;
+  return run_plan<ArcCtx>(h, arc_bytes(h, N), ws, ws_bytes, stream, "ArcFace forward", [&](ArcCtx& c) {
+    void* xin = arc_xin(c, N);
+    int* flag = (int*)(c.scratch - 256);   // the plan's last region, which ends where the scratch starts
+    if (crops) {
+      if (hipMemsetAsync(flag, 0, sizeof(int), c.s) != hipSuccess) return arc_fail(GHOST_EINVAL, "memset failed");
+      const int per = Hs * Ws * 3;
+      hipLaunchKernelGGL(u8_max_kernel, dim3(8, (unsigned)N), dim3(256), 0, c.s, crops, (long)crop_bs, per, flag);
+      const float sh = (float)(Hs - 1) / (float)(112 - 1), sw = (float)(Ws - 1) / (float)(112 - 1);
+      const long P = (long)N * 112 * 112;
+      dim3 grid((unsigned)((P + 255) / 256));
+      if (h->dt == GHOST_F32)
+        hipLaunchKernelGGL(arc_prep_kernel<float>, grid, dim3(256), 0, c.s, crops, (long)crop_bs, N, Hs, Ws, 112, 112,
+                           sh, sw, flag, (float*)xin);
+      else
+        hipLaunchKernelGGL(arc_prep_kernel<bf16>, grid, dim3(256), 0, c.s, crops, (long)crop_bs, N, Hs, Ws, 112, 112,
+                           sh, sw, flag, (bf16*)xin);
+      c.check((int)hipGetLastError(), "arc_prep");
+    } else {
+      c.check(input_to_nhwc(xt_dtype, xt, st, N, 3, 112, 112, h->dt, xin, c.s, 4), "input_to_nhwc");
+    }
+    arc_plan(c, xin, N, emb);
+    return 0;
+  });
 }
 
 }  // namespace
@@ -342,12 +316,11 @@ extern "C" int ghost_arc_create(const int layers[4], int num_features, int dtype
   for (int i = 0; i < 4; ++i)
     if (layers[i] < 1 || layers[i] > 64) return arc_fail(GHOST_EINVAL, "layers[i] out of range");
   if (num_features <= 0 || num_features % 16) return arc_fail(GHOST_EINVAL, "num_features must be a multiple of 16");
-  if (dtype != GHOST_F32 && dtype != GHOST_BF16) return arc_fail(GHOST_EINVAL, "dtype must be f32 or bf16");
+  if (!storage_esz(dtype, false)) return arc_fail(GHOST_EINVAL, "dtype must be f32 or bf16");
   ghost_arc* h = new ghost_arc();
+  h->set_storage(dtype);
   for (int i = 0; i < 4; ++i) h->layers[i] = layers[i];
   h->nf = num_features;
-  h->dt = dtype;
-  h->esz = dtype == GHOST_F32 ? 4 : 2;
   declare(h);
   *out = h;
   return 0;
@@ -356,18 +329,14 @@ extern "C" int ghost_arc_create(const int layers[4], int num_features, int dtype
 extern "C" void ghost_arc_destroy(ghost_arc* h) { delete h; }
 
 extern "C" int ghost_arc_bind(ghost_arc* h, const char* name, const void* p, int64_t numel) {
-  return bind_slot(h ? &h->slots : nullptr, name, p, numel, "empty tensor for ", false);
+  return handle_bind(h, name, p, numel);
 }
 
-extern "C" int ghost_arc_missing(ghost_arc* h) {
-  if (!h) return arc_fail(GHOST_EINVAL, "null handle");
-  return count_missing(h->slots);
-}
+extern "C" int ghost_arc_missing(ghost_arc* h) { return handle_missing(h); }
 
 extern "C" int64_t ghost_arc_workspace_bytes(ghost_arc* h, int N) {
   if (!h || N <= 0) return arc_fail(GHOST_EINVAL, "bad argument");
-  size_t scratch = 0;
-  return arc_bytes(h, N, &scratch);
+  return arc_bytes(h, N).need();
 }
 
 extern "C" int ghost_arc_forward(ghost_arc* h, const void* x, int x_dtype, const int64_t x_strides[4], int N,
@@ -385,9 +354,7 @@ extern "C" int ghost_arc_embed_u8(ghost_arc* h, const uint8_t* crops, int64_t cr
 }
 
 extern "C" int ghost_arc_set_taps(ghost_arc* h, void* const* taps, int ntaps) {
-  if (!h || ntaps < 0 || (ntaps && !taps)) return arc_fail(GHOST_EINVAL, "bad argument");
-  h->taps.assign(taps, taps + ntaps);
-  return 0;
+  return handle_set_taps(h, taps, ntaps);
 }
 
 extern "C" int ghost_arc_match(const float* face_emb, int F, const float* target_emb, int T, int dim,

@@ -34,13 +34,13 @@ using namespace ghost;
 
 static int det_fail(int rc, const std::string& msg) { return ghost::set_last_error(rc, msg); }
 
-struct ghost_det {
-  int dt = GHOST_F32, esz = 4, Hd = 640, Wd = 640;
-  Slots slots;
-  // diagnostic taps (ghost_det_set_taps): the stored outputs of the stem (after the pool), stage 1, stage 4 and P3
-  void* taps[4] = {nullptr, nullptr, nullptr, nullptr};
-  // (N, detect) -> plan end, scratch: the dry run's result, kept so that a call does not repeat it
-  std::map<std::pair<int, bool>, std::pair<size_t, size_t>> sized;
+// diagnostic taps (ghost_det_set_taps): the stored outputs of the stem (after the pool), stage 1, stage 4 and P3
+struct ghost_det : Handle {
+  static constexpr int kTaps = 4;
+  static constexpr bool kAligned16 = true;
+  int Hd = 640, Wd = 640;
+  // (N, detect) -> the dry run's result, kept so that a call does not repeat it
+  std::map<std::pair<int, bool>, PlanSize> sized;
 };
 
 namespace {
@@ -50,11 +50,8 @@ const int kNBlocks[4] = {3, 4, 2, 3};
 constexpr int kNeck = 56, kTower = 80;
 constexpr int kMaxBatch = 4096;
 
-struct DetCtx : PlanCtx {
-  ghost_det* h = nullptr;
+struct DetCtx : HandleCtx<ghost_det> {
   std::string* list = nullptr;   // ghost_det_plan: one line per launch of the dry run
-  const void* W(const std::string& name) { return PlanCtx::W(h->slots, name); }
-  const float* F(const std::string& name) { return (const float*)W(name); }
   void line(const char* fmt, ...) __attribute__((format(printf, 2, 3))) {
     if (!list) return;
     char buf[256];
@@ -68,11 +65,6 @@ struct DetCtx : PlanCtx {
 };
 
 struct Outs { float* cls[3]; float* reg[3]; float* kps[3]; };
-
-void tap(DetCtx& c, int i, const void* src, size_t bytes) {
-  if (c.dry || !c.ok() || !c.h->taps[i]) return;
-  c.check((int)hipMemcpyAsync(c.h->taps[i], src, bytes, hipMemcpyDeviceToDevice, c.s), "tap copy");
-}
 
 // one conv unit of the table: y = act(conv(x) + bias + res)
 void conv(DetCtx& c, const std::string& name, const void* x, int N, int H, int W, int cin, int cout, int k, int stride,
@@ -118,7 +110,7 @@ void det_plan(DetCtx& c, const uint8_t* canvas, int64_t bstride, int N, const Ou
   conv(c, "backbone.stem.6", S1, N, H2, W2, kDetStemC, 56, 3, 1, 1, true, nullptr, S2, dt);
   c.line("maxpool in=%dx%d c=56", H2, W2);
   if (c.ok() && !c.dry) c.check(det_maxpool(dt, S2, N, H2, W2, 56, P[0], c.s), "maxpool");
-  tap(c, 0, P[0], px4 * 56 * es);
+  c.tap(0, P[0], px4 * 56 * es);
   void* cur = P[0];
   int cin = 56, H = H4, W = W4;
   for (int st = 0; st < 4; ++st) {
@@ -137,8 +129,8 @@ void det_plan(DetCtx& c, const uint8_t* canvas, int64_t bstride, int N, const Ou
       conv(c, nm + ".conv2", T, N, Ho, Wo, pl, pl, 3, 1, 1, true, idn, out, dt);
       cur = out; cin = pl; H = Ho; W = Wo;
     }
-    if (st == 0) tap(c, 1, cur, px4 * 56 * es);
-    if (st == 3) tap(c, 2, cur, px8 / 16 * 224 * es);
+    if (st == 0) c.tap(1, cur, px4 * 56 * es);
+    if (st == 3) c.tap(2, cur, px8 / 16 * 224 * es);
   }
   // ---- PAFPN ----
   const int Hl[3] = {Hd / 8, Hd / 16, Hd / 32}, Wl[3] = {Wd / 8, Wd / 16, Wd / 32};
@@ -170,7 +162,7 @@ void det_plan(DetCtx& c, const uint8_t* canvas, int64_t bstride, int N, const Ou
     conv(c, "neck.pafpn_convs." + std::to_string(i) + ".conv", J[i + 1], N, Hl[i + 1], Wl[i + 1], kNeck, kNeck, 3, 1, 1,
          false, nullptr, Pm[i + 1], dt);
   }
-  tap(c, 3, Pm[0], px8 * kNeck * es);
+  c.tap(3, Pm[0], px8 * kNeck * es);
   // ---- heads ----
   void* U[2] = {c.alloc(px8 * kTower * es), c.alloc(px8 * kTower * es)};
   for (int l = 0; l < 3; ++l) {
@@ -234,14 +226,18 @@ Front front(DetCtx& c, int N, bool detect) {
 }
 
 // detect: with the nine maps and the decode workspace in the workspace (forward's maps are the caller's)
-int64_t det_bytes(ghost_det* h, int N, bool detect, size_t* plan_end, size_t* scratch, std::string* list = nullptr) {
-  if ((int64_t)N * (h->Hd / 2) * (h->Wd / 2) > 0x7fffffffLL)
-    return det_fail(GHOST_EINVAL, "batch x det_size too large for one call (N * Hd/2 * Wd/2 must fit 31 bits)");
+// A failure (rc set) has set the last error.
+PlanSize det_bytes(ghost_det* h, int N, bool detect, std::string* list = nullptr) {
+  PlanSize z;
+  if ((int64_t)N * (h->Hd / 2) * (h->Wd / 2) > 0x7fffffffLL) {
+    z.rc = det_fail(GHOST_EINVAL, "batch x det_size too large for one call (N * Hd/2 * Wd/2 must fit 31 bits)");
+    return z;
+  }
   const auto key = std::make_pair(N, detect);
-  auto it = h->sized.find(key);
-  if (it == h->sized.end() || list) {
-    DetCtx c{};
-    c.h = h; c.dry = true; c.list = list;
+  const auto it = h->sized.find(key);
+  if (it != h->sized.end() && !list) return it->second;
+  z = size_plan<DetCtx>(h, [&](DetCtx& c) {
+    c.list = list;
     c.line("letterbox out=%dx%d", h->Hd, h->Wd);
     const Front f = front(c, N, detect);
     det_plan(c, f.canvas, (int64_t)h->Hd * h->Wd * 3, N, f.maps);
@@ -249,13 +245,14 @@ int64_t det_bytes(ghost_det* h, int N, bool detect, size_t* plan_end, size_t* sc
       c.line("decode cap=%d", kDetMaxCap);
       c.line("nms cap=%d", kDetMaxCap);
     }
-    if (!c.ok()) return det_fail(c.rc, "detector plan: " + c.where);
-    if (h->sized.size() >= 64) h->sized.clear();
-    it = h->sized.insert_or_assign(key, std::make_pair(align_up(c.off), c.scratch_need)).first;
+  });
+  if (z.rc) {
+    det_fail(z.rc, "detector plan: " + z.where);
+    return z;
   }
-  *plan_end = it->second.first;
-  *scratch = it->second.second;
-  return (int64_t)(*plan_end + *scratch + 256);
+  if (h->sized.size() >= 64) h->sized.clear();
+  h->sized[key] = z;
+  return z;
 }
 
 struct DetectArgs {
@@ -266,51 +263,39 @@ struct DetectArgs {
 
 int run_det(ghost_det* h, const uint8_t* frames, int64_t fstride, int N, int H, int W, int new_h, int new_w,
             float* const* maps, const DetectArgs* da, void* ws, int64_t ws_bytes, void* stream) {
-  if (!h) return det_fail(GHOST_EINVAL, "null handle");
-  if (N < 0 || N > kMaxBatch) return det_fail(GHOST_EINVAL, "batch must be in 0..4096");
+  if (const int rc = check_batch(h, N, 0, kMaxBatch)) return rc;
   if (N == 0) return GHOST_OK;
   if (!frames || H <= 0 || W <= 0 || fstride < (int64_t)H * W * 3) return det_fail(GHOST_EINVAL, "bad frames");
   if (new_h <= 0 || new_w <= 0 || new_h > h->Hd || new_w > h->Wd)
     return det_fail(GHOST_EINVAL, "the resized frame must fit det_size");
   if (count_missing(h->slots)) return GHOST_ENOTREADY;
-  size_t plan_end = 0, scratch = 0;
-  const int64_t need = det_bytes(h, N, da != nullptr, &plan_end, &scratch);
-  if (need < 0) return (int)need;
-  if (!ws || ws_bytes < need) return det_fail(GHOST_ENOWS, "workspace too small: need " + std::to_string(need));
-  DetCtx c{};
-  c.h = h; c.dry = false;
-  c.base = align_up(ws);
-  c.s = (hipStream_t)stream;
-  c.scratch = c.base + plan_end;
-  c.scratch_cap = scratch;
-  Front f = front(c, N, da != nullptr);
-  if (maps)
-    for (int l = 0; l < 3; ++l) { f.maps.cls[l] = maps[l]; f.maps.reg[l] = maps[3 + l]; f.maps.kps[l] = maps[6 + l]; }
-  c.check(det_letterbox(frames, fstride, N, H, W, new_h, new_w, f.canvas, h->Hd, h->Wd, c.s), "letterbox");
-  det_plan(c, f.canvas, (int64_t)h->Hd * h->Wd * 3, N, f.maps);
-  if (c.ok() && da) {
-    DetMaps m;
-    for (int l = 0; l < 3; ++l) { m.cls[l] = f.maps.cls[l]; m.reg[l] = f.maps.reg[l]; m.kps[l] = f.maps.kps[l]; }
-    c.check(det_decode_nms(m, N, h->Hd, h->Wd, da->thresh, da->det_scale, da->nms_thresh, kDetMaxCap, da->max_faces,
-                           da->det, da->kps, da->anchor, da->count, f.dws, f.dws_bytes, c.s), "decode + nms");
-  }
-  if (!c.ok())
-    return det_fail(c.rc, "detector failed at " + c.where +
-                              (c.rc > 0 ? std::string(": ") + hipGetErrorString((hipError_t)c.rc) : std::string()));
-  return 0;
+  const PlanSize z = det_bytes(h, N, da != nullptr);
+  if (z.rc) return z.rc;
+  return run_plan<DetCtx>(h, z, ws, ws_bytes, stream, "detector", [&](DetCtx& c) {
+    Front f = front(c, N, da != nullptr);
+    if (maps)
+      for (int l = 0; l < 3; ++l) { f.maps.cls[l] = maps[l]; f.maps.reg[l] = maps[3 + l]; f.maps.kps[l] = maps[6 + l]; }
+    c.check(det_letterbox(frames, fstride, N, H, W, new_h, new_w, f.canvas, h->Hd, h->Wd, c.s), "letterbox");
+    det_plan(c, f.canvas, (int64_t)h->Hd * h->Wd * 3, N, f.maps);
+    if (c.ok() && da) {
+      DetMaps m;
+      for (int l = 0; l < 3; ++l) { m.cls[l] = f.maps.cls[l]; m.reg[l] = f.maps.reg[l]; m.kps[l] = f.maps.kps[l]; }
+      c.check(det_decode_nms(m, N, h->Hd, h->Wd, da->thresh, da->det_scale, da->nms_thresh, kDetMaxCap, da->max_faces,
+                             da->det, da->kps, da->anchor, da->count, f.dws, f.dws_bytes, c.s), "decode + nms");
+    }
+    return 0;
+  });
 }
 
 }  // namespace
 
 extern "C" int ghost_det_create(int dtype, int det_w, int det_h, ghost_det** out) {
   if (!out) return det_fail(GHOST_EINVAL, "null argument");
-  if (dtype != GHOST_F32 && dtype != GHOST_BF16 && dtype != GHOST_F16)
-    return det_fail(GHOST_EINVAL, "dtype must be f32, bf16 or f16");
+  if (!storage_esz(dtype)) return det_fail(GHOST_EINVAL, "dtype must be f32, bf16 or f16");
   if (det_w <= 0 || det_h <= 0 || det_w % 32 || det_h % 32 || det_w > 8192 || det_h > 8192)
     return det_fail(GHOST_EINVAL, "det_size must be positive multiples of 32, at most 8192");
   ghost_det* h = new ghost_det();
-  h->dt = dtype;
-  h->esz = dtype == GHOST_F32 ? 4 : 2;
+  h->set_storage(dtype);
   h->Wd = det_w;
   h->Hd = det_h;
   declare(h);
@@ -321,27 +306,22 @@ extern "C" int ghost_det_create(int dtype, int det_w, int det_h, ghost_det** out
 extern "C" void ghost_det_destroy(ghost_det* h) { delete h; }
 
 extern "C" int ghost_det_bind(ghost_det* h, const char* name, const void* p, int64_t numel) {
-  return bind_slot(h ? &h->slots : nullptr, name, p, numel, "empty tensor for ", true);
+  return handle_bind(h, name, p, numel);
 }
 
-extern "C" int ghost_det_missing(ghost_det* h) {
-  if (!h) return det_fail(GHOST_EINVAL, "null handle");
-  return count_missing(h->slots);
-}
+extern "C" int ghost_det_missing(ghost_det* h) { return handle_missing(h); }
 
 extern "C" int64_t ghost_det_workspace_bytes(ghost_det* h, int N) {
   if (!h || N < 0 || N > kMaxBatch) return det_fail(GHOST_EINVAL, "bad argument");
   if (N == 0) return 256;
-  size_t plan_end = 0, scratch = 0;
-  return det_bytes(h, N, true, &plan_end, &scratch);
+  return det_bytes(h, N, true).need();
 }
 
 extern "C" int64_t ghost_det_plan(ghost_det* h, int N, char* buf, int64_t cap) {
   if (!h || N <= 0 || N > kMaxBatch || cap < 0 || (cap > 0 && !buf)) return det_fail(GHOST_EINVAL, "bad argument");
   std::string text;
-  size_t plan_end = 0, scratch = 0;
-  const int64_t rc = det_bytes(h, N, true, &plan_end, &scratch, &text);
-  if (rc < 0) return rc;
+  const PlanSize z = det_bytes(h, N, true, &text);
+  if (z.rc) return z.rc;
   if (cap > 0) snprintf(buf, (size_t)cap, "%s", text.c_str());
   return (int64_t)text.size() + 1;
 }
@@ -367,7 +347,5 @@ extern "C" int ghost_det_detect_u8(ghost_det* h, const uint8_t* frames_bgr, int6
 }
 
 extern "C" int ghost_det_set_taps(ghost_det* h, void* const* taps, int ntaps) {
-  if (!h || (ntaps != 0 && ntaps != 4) || (ntaps && !taps)) return det_fail(GHOST_EINVAL, "bad argument (0 or 4 taps)");
-  for (int i = 0; i < 4; ++i) h->taps[i] = ntaps ? taps[i] : nullptr;
-  return 0;
+  return handle_set_taps(h, taps, ntaps);
 }

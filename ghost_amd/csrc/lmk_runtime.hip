@@ -26,11 +26,10 @@ using namespace ghost;
 
 static int lmk_fail(int rc, const std::string& msg) { return ghost::set_last_error(rc, msg); }
 
-struct ghost_lmk {
-  int dt = GHOST_F32, esz = 4;
-  Slots slots;
-  // diagnostic taps (ghost_lmk_set_taps): the stored outputs of conv_2, conv_7, conv_14 and conv_15
-  void* taps[4] = {nullptr, nullptr, nullptr, nullptr};
+// diagnostic taps (ghost_lmk_set_taps): the stored outputs of conv_2, conv_7, conv_14 and conv_15
+struct ghost_lmk : Handle {
+  static constexpr int kTaps = 4;
+  static constexpr bool kAligned16 = true;
 };
 
 namespace {
@@ -51,18 +50,9 @@ static int unfused_mask() {
   return v;
 }
 
-struct LmkCtx : PlanCtx {
-  ghost_lmk* h = nullptr;
-  const void* W(const std::string& name) { return PlanCtx::W(h->slots, name); }
-  const float* F(const std::string& name) { return (const float*)W(name); }
-};
+typedef HandleCtx<ghost_lmk> LmkCtx;
 
 std::string cname(int k) { return "c" + std::to_string(k); }
-
-void tap(LmkCtx& c, int i, const void* src, size_t bytes) {
-  if (c.dry || !c.ok() || !c.h->taps[i]) return;
-  c.check((int)hipMemcpyAsync(c.h->taps[i], src, bytes, hipMemcpyDeviceToDevice, c.s), "tap copy");
-}
 
 // x192: uint8 [N,192,192,3], bstride bytes apart
 void lmk_plan(LmkCtx& c, const uint8_t* x192, int64_t bstride, int bgr, int N, float* pred, float* lmk) {
@@ -102,9 +92,9 @@ void lmk_plan(LmkCtx& c, const uint8_t* x192, int64_t bstride, int bgr, int N, f
     }
     cur ^= 1;
     const size_t bytes = (size_t)N * ho * ho * b.cout * es;
-    if (b.k == 2) tap(c, 0, X[cur], bytes);
-    if (b.k == 7) tap(c, 1, X[cur], bytes);
-    if (b.k == 14) tap(c, 2, X[cur], bytes);
+    if (b.k == 2) c.tap(0, X[cur], bytes);
+    if (b.k == 7) c.tap(1, X[cur], bytes);
+    if (b.k == 14) c.tap(2, X[cur], bytes);
   }
   {
     ConvDesc g = conv_desc(dt, dt, X[cur], N, 6, 512, 512, c.W("c15.w"), 64, CONV_FWD, 3, 2, 1, X[cur ^ 1], 64);
@@ -112,7 +102,7 @@ void lmk_plan(LmkCtx& c, const uint8_t* x192, int64_t bstride, int bgr, int N, f
     if (c.dry) c.need_scratch(conv_workspace_bytes(g));
     else if (c.ok()) c.check(conv_launch(g, c.scratch, c.scratch_cap, c.s), "c15");
     cur ^= 1;
-    tap(c, 3, X[cur], (size_t)N * 9 * 64 * es);
+    c.tap(3, X[cur], (size_t)N * 9 * 64 * es);
   }
   const float *fw = c.F("fc.w"), *fb = c.F("fc.bias");
   if (!c.dry && c.ok()) c.check(lmk_head(dt, X[cur], N, 576, kOut, fw, fb, pred, lmk, c.s), "head");
@@ -140,63 +130,45 @@ Front front(LmkCtx& c, int N) {
   return f;
 }
 
-int64_t lmk_bytes(ghost_lmk* h, int N, size_t* plan_end, size_t* scratch) {
-  LmkCtx c{};
-  c.h = h; c.dry = true;
-  const Front f = front(c, N);
-  lmk_plan(c, f.x192, (int64_t)kIn * kIn * 3, 1, N, (float*)uintptr_t(0x30000000), nullptr);
-  if (!c.ok()) return c.rc;
-  *plan_end = align_up(c.off);
-  *scratch = c.scratch_need;
-  return (int64_t)(*plan_end + c.scratch_need + 256);
+PlanSize lmk_bytes(ghost_lmk* h, int N) {
+  return size_plan<LmkCtx>(h, [&](LmkCtx& c) {
+    const Front f = front(c, N);
+    lmk_plan(c, f.x192, (int64_t)kIn * kIn * 3, 1, N, (float*)uintptr_t(0x30000000), nullptr);
+  });
 }
 
 int run_lmk(ghost_lmk* h, const uint8_t* x192, int64_t xstride, int bgr, const uint8_t* crops, int64_t crop_bs, int N,
             float* pred, float* lmk, void* ws, int64_t ws_bytes, void* stream) {
-  if (!h) return lmk_fail(GHOST_EINVAL, "null handle");
-  if (N < 0 || N > 65535) return lmk_fail(GHOST_EINVAL, "batch must be in 0..65535");
+  if (const int rc = check_batch(h, N, 0, 65535)) return rc;
   if (N == 0) return GHOST_OK;
   if (count_missing(h->slots)) return GHOST_ENOTREADY;
-  size_t plan_end = 0, scratch = 0;
-  const int64_t need = lmk_bytes(h, N, &plan_end, &scratch);
-  if (need < 0) return lmk_fail((int)need, "plan sizing failed");
-  if (!ws || ws_bytes < need) return lmk_fail(GHOST_ENOWS, "workspace too small: need " + std::to_string(need));
-  LmkCtx c{};
-  c.h = h; c.dry = false;
-  c.base = align_up(ws);
-  c.s = (hipStream_t)stream;
-  c.scratch = c.base + plan_end;
-  c.scratch_cap = scratch;
-  const Front f = front(c, N);
-  if (crops) {
-    // cv2.warpAffine(crop, M, (192, 192), borderValue=0.0): the maps are cv2.invertAffineTransform(M) in double
-    const double Dv = 1.0 / (kM[0] * kM[4] - kM[1] * kM[3]);
-    const double a11 = kM[4] * Dv, a22 = kM[0] * Dv, a12 = -kM[1] * Dv, a21 = -kM[3] * Dv;
-    const double inv[6] = {a11, a12, -a11 * kM[2] - a12 * kM[5], a21, a22, -a21 * kM[2] - a22 * kM[5]};
-    c.check(lmk_fill_maps(f.fi, f.maps, N, inv, c.s), "fill maps");
-    if (c.ok() && ghost_align_crops_u8(crops, crop_bs, N, kCrop, kCrop, f.fi, f.maps, nullptr, N, kIn, f.x192,
-                                       (int64_t)kIn * kIn * 3, nullptr, 0, 0, stream) != 0)
-      return GHOST_EINVAL;   // the last error is ghost_align_crops_u8's
-    x192 = f.x192;
-    xstride = (int64_t)kIn * kIn * 3;
-    bgr = 1;
-  }
-  lmk_plan(c, x192, xstride, bgr, N, pred, lmk);
-  if (!c.ok())
-    return lmk_fail(c.rc, "landmark forward failed at " + c.where +
-                              (c.rc > 0 ? std::string(": ") + hipGetErrorString((hipError_t)c.rc) : std::string()));
-  return 0;
+  return run_plan<LmkCtx>(h, lmk_bytes(h, N), ws, ws_bytes, stream, "landmark forward", [&](LmkCtx& c) {
+    const Front f = front(c, N);
+    if (crops) {
+      // cv2.warpAffine(crop, M, (192, 192), borderValue=0.0): the maps are cv2.invertAffineTransform(M) in double
+      const double Dv = 1.0 / (kM[0] * kM[4] - kM[1] * kM[3]);
+      const double a11 = kM[4] * Dv, a22 = kM[0] * Dv, a12 = -kM[1] * Dv, a21 = -kM[3] * Dv;
+      const double inv[6] = {a11, a12, -a11 * kM[2] - a12 * kM[5], a21, a22, -a21 * kM[2] - a22 * kM[5]};
+      c.check(lmk_fill_maps(f.fi, f.maps, N, inv, c.s), "fill maps");
+      if (c.ok() && ghost_align_crops_u8(crops, crop_bs, N, kCrop, kCrop, f.fi, f.maps, nullptr, N, kIn, f.x192,
+                                         (int64_t)kIn * kIn * 3, nullptr, 0, 0, stream) != 0)
+        return (int)GHOST_EINVAL;   // the last error is ghost_align_crops_u8's
+      x192 = f.x192;
+      xstride = (int64_t)kIn * kIn * 3;
+      bgr = 1;
+    }
+    lmk_plan(c, x192, xstride, bgr, N, pred, lmk);
+    return 0;
+  });
 }
 
 }  // namespace
 
 extern "C" int ghost_lmk_create(int dtype, ghost_lmk** out) {
   if (!out) return lmk_fail(GHOST_EINVAL, "null argument");
-  if (dtype != GHOST_F32 && dtype != GHOST_BF16 && dtype != GHOST_F16)
-    return lmk_fail(GHOST_EINVAL, "dtype must be f32, bf16 or f16");
+  if (!storage_esz(dtype)) return lmk_fail(GHOST_EINVAL, "dtype must be f32, bf16 or f16");
   ghost_lmk* h = new ghost_lmk();
-  h->dt = dtype;
-  h->esz = dtype == GHOST_F32 ? 4 : 2;
+  h->set_storage(dtype);
   declare(h);
   *out = h;
   return 0;
@@ -205,19 +177,15 @@ extern "C" int ghost_lmk_create(int dtype, ghost_lmk** out) {
 extern "C" void ghost_lmk_destroy(ghost_lmk* h) { delete h; }
 
 extern "C" int ghost_lmk_bind(ghost_lmk* h, const char* name, const void* p, int64_t numel) {
-  return bind_slot(h ? &h->slots : nullptr, name, p, numel, "empty tensor for ", true);
+  return handle_bind(h, name, p, numel);
 }
 
-extern "C" int ghost_lmk_missing(ghost_lmk* h) {
-  if (!h) return lmk_fail(GHOST_EINVAL, "null handle");
-  return count_missing(h->slots);
-}
+extern "C" int ghost_lmk_missing(ghost_lmk* h) { return handle_missing(h); }
 
 extern "C" int64_t ghost_lmk_workspace_bytes(ghost_lmk* h, int N) {
   if (!h || N < 0 || N > 65535) return lmk_fail(GHOST_EINVAL, "bad argument");
   if (N == 0) return 256;
-  size_t plan_end = 0, scratch = 0;
-  return lmk_bytes(h, N, &plan_end, &scratch);
+  return lmk_bytes(h, N).need();
 }
 
 extern "C" int ghost_lmk_forward(ghost_lmk* h, const uint8_t* x192, int64_t x_batch_stride, int bgr, int N,
@@ -236,7 +204,5 @@ extern "C" int ghost_lmk_landmarks_u8(ghost_lmk* h, const uint8_t* crops224_bgr,
 }
 
 extern "C" int ghost_lmk_set_taps(ghost_lmk* h, void* const* taps, int ntaps) {
-  if (!h || (ntaps != 0 && ntaps != 4) || (ntaps && !taps)) return lmk_fail(GHOST_EINVAL, "bad argument (0 or 4 taps)");
-  for (int i = 0; i < 4; ++i) h->taps[i] = ntaps ? taps[i] : nullptr;
-  return 0;
+  return handle_set_taps(h, taps, ntaps);
 }

@@ -12,6 +12,7 @@ There is no CPU path.  The graph and parity against onnxruntime are unpinned (DE
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Mapping, Optional
 
@@ -20,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .._packed import PackedModule, WorkspaceCache
+from .._packed import NativeRuntime, PackedModule, load_named, u8_rows
 from .pack import (MAX_CANDIDATES, NMS_THRESH, NUM_ANCHORS, STRIDES, TAPS, letterbox_geometry, pack_detector,
                    param_specs, units)
 
@@ -29,37 +30,10 @@ from .pack import (MAX_CANDIDATES, NMS_THRESH, NUM_ANCHORS, STRIDES, TAPS, lette
 CHUNK_640 = 8
 
 
-class _Runtime:
+class _Runtime(NativeRuntime):
     def __init__(self, dtype, det_size, slots):
-        self.lib = _lib.load()
-        self.dtype = dtype
+        super().__init__("det", "detector ", dtype, slots, _lib.gdtype(dtype), det_size[0], det_size[1])
         self.det_size = det_size
-        h = C.c_void_p()
-        _lib.check(self.lib.ghost_det_create(_lib.gdtype(dtype), det_size[0], det_size[1], C.byref(h)),
-                   "ghost_det_create")
-        self.h = h
-        self.slots = slots
-        self.ws = WorkspaceCache()   # (chunk, stream) -> workspace
-        for name, t in slots.items():
-            _lib.check(self.lib.ghost_det_bind(h, name.encode(), t.data_ptr(), t.numel()), f"bind {name}")
-        if self.lib.ghost_det_missing(h) != 0:
-            _lib.check(-2, "detector weights incomplete")
-
-    def __del__(self):
-        try:
-            if self.h:
-                self.lib.ghost_det_destroy(self.h)
-        except Exception:
-            pass
-
-
-def _to_tensor(v) -> torch.Tensor:
-    if torch.is_tensor(v):
-        return v.detach()
-    if hasattr(v, "asnumpy"):
-        v = v.asnumpy()
-    a = np.asarray(v)      # (np.ascontiguousarray would turn bbox_scale's 0-d array into [1])
-    return torch.from_numpy(a if a.flags.c_contiguous else np.ascontiguousarray(a))
 
 
 class SCRFD(PackedModule):
@@ -109,18 +83,7 @@ class SCRFD(PackedModule):
     def load_arrays(self, mapping: Mapping) -> None:
         """Load ``{name: array}`` with exactly ``pack.param_specs()``'s names and shapes; values are numpy arrays,
         torch tensors or anything with ``.asnumpy()``."""
-        want = dict(param_specs())
-        missing = sorted(set(want) - set(mapping))
-        extra = sorted(set(mapping) - set(want))
-        if missing or extra:
-            raise KeyError(f"ghost_amd: SCRFD parameters do not match: missing {missing}, unexpected {extra}")
-        own = dict(self.named_parameters())
-        with torch.no_grad():
-            for n, shape in want.items():
-                t = _to_tensor(mapping[n])
-                if tuple(t.shape) != tuple(shape):
-                    raise ValueError(f"ghost_amd: {n} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-                own[n].copy_(t.to(own[n].device, own[n].dtype))
+        load_named(dict(self.named_parameters()), dict(param_specs()), mapping, "SCRFD")
         self._invalidate()
 
     def _dtype(self):
@@ -140,14 +103,7 @@ class SCRFD(PackedModule):
     def _workspace(self, rt, dev):
         """One workspace per stream, sized for a full chunk and used for a shorter last chunk as well: a module holds
         at most ``ghost_det_workspace_bytes(chunk_frames())`` per stream it is called on (4 streams are kept)."""
-        step = self.chunk_frames()
-
-        def nbytes():
-            n = rt.lib.ghost_det_workspace_bytes(rt.h, step)
-            if n < 0:
-                _lib.check(int(n), "detector workspace sizing")
-            return n
-        return rt.ws.get((step, _lib.stream_ptr(dev)), nbytes, dev)
+        return rt.batch_workspace(self.chunk_frames(), dev)
 
     def plan(self, N: int) -> list:
         """The launches of one detect call over N frames (ghost_det_plan; needs no device)."""
@@ -171,10 +127,7 @@ class SCRFD(PackedModule):
         _lib.require_gpu(x, what)
         if x.dtype != torch.uint8 or x.ndim != 4 or x.shape[3] != 3 or x.shape[1] < 1 or x.shape[2] < 1:
             raise RuntimeError(f"ghost_amd: {what} takes uint8 BGR frames [F,H,W,3], got {x.dtype} {tuple(x.shape)}")
-        H, W = x.shape[1], x.shape[2]
-        if x.shape[0] > 1 and x[0].stride() != (W * 3, 3, 1) or x.shape[0] == 1 and not x.is_contiguous():
-            x = x.contiguous()
-        return x
+        return u8_rows(x)
 
     def _maps(self, N, dev):
         Wd, Hd = self.det_size
@@ -183,28 +136,21 @@ class SCRFD(PackedModule):
             out += [torch.empty(N, Hd // s, Wd // s, ch, dtype=torch.float32, device=dev) for s in STRIDES]
         return out
 
-    def _forward(self, x, taps=None):
+    def _forward(self, x, bs, taps=None):
         rt = self._runtime(x.device)
         F_, H, W = x.shape[:3]
         maps = self._maps(F_, x.device)
         if F_:
             new_h, new_w, _ = letterbox_geometry(H, W, self.det_size)
             ws = self._workspace(rt, x.device)
-            bs = x.stride(0) if F_ > 1 else H * W * 3
             step = self.chunk_frames()
-            try:
-                for a in range(0, F_, step):
-                    n = min(step, F_ - a)
-                    if taps is not None:
-                        tp = (C.c_void_p * 4)(*[t[a].data_ptr() for t in taps])
-                        _lib.check(rt.lib.ghost_det_set_taps(rt.h, tp, 4), "detector taps")
-                    ptrs = (C.c_void_p * 9)(*[t[a].data_ptr() for t in maps])
+            for a in range(0, F_, step):
+                n = min(step, F_ - a)
+                ptrs = (C.c_void_p * 9)(*[t[a].data_ptr() for t in maps])
+                with rt.taps([t[a].data_ptr() for t in taps], "detector taps") if taps else contextlib.nullcontext():
                     _lib.check(rt.lib.ghost_det_forward_u8(rt.h, x[a].data_ptr(), bs, n, H, W, new_h, new_w, ptrs,
                                                            ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)),
                                "SCRFD.forward")
-            finally:
-                if taps is not None:
-                    rt.lib.ghost_det_set_taps(rt.h, None, 0)
         return [t.permute(0, 3, 1, 2) for t in maps]
 
     @torch.no_grad()
@@ -212,17 +158,17 @@ class SCRFD(PackedModule):
         """frames: uint8 BGR [F,H,W,3] on the GPU -> the nine maps as float32 NCHW views: scores [F,2,Hl,Wl], boxes
         [F,8,Hl,Wl] and keypoints [F,20,Hl,Wl] for strides 8, 16, 32 (scores x 3, boxes x 3, keypoints x 3).  Frames
         go to the native call ``chunk_frames()`` at a time, as in ``detect_frames``."""
-        return self._forward(self._check_frames(frames, "SCRFD.forward"))
+        return self._forward(*self._check_frames(frames, "SCRFD.forward"))
 
     @torch.no_grad()
     def forward_taps(self, frames: torch.Tensor):
         """forward + the stored outputs of the stem (after its pool), stage 1, stage 4 and P3 as NCHW views in the
         compute dtype."""
-        x = self._check_frames(frames, "SCRFD.forward_taps")
+        x, bs = self._check_frames(frames, "SCRFD.forward_taps")
         rt = self._runtime(x.device)
         Wd, Hd = self.det_size
         bufs = [torch.empty(x.shape[0], Hd // s, Wd // s, c, dtype=rt.dtype, device=x.device) for _n, c, s in TAPS]
-        maps = self._forward(x, bufs)
+        maps = self._forward(x, bs, bufs)
         return maps, [t.permute(0, 3, 1, 2) for t in bufs]
 
     @torch.no_grad()
@@ -233,7 +179,7 @@ class SCRFD(PackedModule):
         candidates), on the device, in kept order and zero beyond (with ``return_anchor`` also the kept candidates'
         anchor indices, int32 [F,max_faces]).  Nothing is copied to the host and nothing synchronises; ``check_counts``
         judges the counts once they are on the host.  Frames go to the native call ``chunk_frames()`` at a time."""
-        x = self._check_frames(frames, "SCRFD.detect_frames")
+        x, bs = self._check_frames(frames, "SCRFD.detect_frames")
         if max_faces <= 0:
             raise ValueError("ghost_amd: max_faces must be positive")
         rt = self._runtime(x.device)
@@ -248,7 +194,6 @@ class SCRFD(PackedModule):
         ws = self._workspace(rt, dev) if F_ else None
         for a in range(0, F_, step):
             n = min(step, F_ - a)
-            bs = x.stride(0) if F_ > 1 else H * W * 3
             _lib.check(rt.lib.ghost_det_detect_u8(rt.h, x[a].data_ptr(), bs, n, H, W, new_h, new_w, det_scale,
                                                   float(thresh), NMS_THRESH, max_faces, det[a].data_ptr(),
                                                   kps[a].data_ptr(), anchor[a].data_ptr(), count[a].data_ptr(),

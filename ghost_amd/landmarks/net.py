@@ -11,7 +11,6 @@ mxnet is unpinned: no mxnet and no checkpoint are available offline.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Mapping, Optional
 
 import numpy as np
@@ -19,38 +18,13 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .._packed import PackedModule, WorkspaceCache
+from .._packed import NativeRuntime, PackedModule, load_named, u8_rows
 from .pack import CROP_SIZE, IN_SIZE, N_POINTS, TAPS, pack_landmark, param_specs
 
 
-class _Runtime:
+class _Runtime(NativeRuntime):
     def __init__(self, dtype, slots):
-        self.lib = _lib.load()
-        self.dtype = dtype
-        h = C.c_void_p()
-        _lib.check(self.lib.ghost_lmk_create(_lib.gdtype(dtype), C.byref(h)), "ghost_lmk_create")
-        self.h = h
-        self.slots = slots
-        self.ws = WorkspaceCache()   # (N, stream) -> workspace
-        for name, t in slots.items():
-            _lib.check(self.lib.ghost_lmk_bind(h, name.encode(), t.data_ptr(), t.numel()), f"bind {name}")
-        if self.lib.ghost_lmk_missing(h) != 0:
-            _lib.check(-2, "landmark weights incomplete")
-
-    def __del__(self):
-        try:
-            if self.h:
-                self.lib.ghost_lmk_destroy(self.h)
-        except Exception:
-            pass
-
-
-def _to_tensor(v) -> torch.Tensor:
-    if torch.is_tensor(v):
-        return v.detach()
-    if hasattr(v, "asnumpy"):
-        v = v.asnumpy()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+        super().__init__("lmk", "landmark ", dtype, slots, _lib.gdtype(dtype))
 
 
 class Landmark106(PackedModule):
@@ -84,19 +58,9 @@ class Landmark106(PackedModule):
             for k, v in m.items():
                 k = k.split(":", 1)[1] if k.startswith(("arg:", "aux:")) else k
                 given[k] = v
-        want = {n: s for n, s, _ in param_specs()}
-        missing = sorted(set(want) - set(given))
-        extra = sorted(set(given) - set(want))
-        if missing or extra:
-            raise KeyError(f"ghost_amd: 2d106det parameters do not match: missing {missing}, unexpected {extra}")
         own = dict(self.named_parameters())
         own.update(dict(self.named_buffers()))
-        with torch.no_grad():
-            for n, shape in want.items():
-                t = _to_tensor(given[n])
-                if tuple(t.shape) != tuple(shape):
-                    raise ValueError(f"ghost_amd: {n} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-                own[n].copy_(t.to(own[n].device, own[n].dtype))
+        load_named(own, {n: s for n, s, _ in param_specs()}, given, "2d106det")
         self._invalidate()
 
     def _dtype(self):
@@ -108,36 +72,25 @@ class Landmark106(PackedModule):
         dt = self._dtype()
         return self._cached_runtime(device, dt, lambda sd: _Runtime(dt, pack_landmark(sd, dt)))
 
-    def _workspace(self, rt, N, dev):
-        def nbytes():
-            n = rt.lib.ghost_lmk_workspace_bytes(rt.h, N)
-            if n < 0:
-                _lib.check(int(n), "landmark workspace sizing")
-            return n
-        return rt.ws.get((N, _lib.stream_ptr(dev)), nbytes, dev)
-
     # -- execution -------------------------------------------------------------------
     @staticmethod
     def _check_u8(x, size, what):
         _lib.require_gpu(x, what)
         if x.dtype != torch.uint8 or x.ndim != 4 or tuple(x.shape[1:]) != (size, size, 3):
             raise RuntimeError(f"ghost_amd: {what} takes uint8 [N,{size},{size},3], got {x.dtype} {tuple(x.shape)}")
-        if x.shape[0] > 1 and x[0].stride() != (size * 3, 3, 1) or x.shape[0] == 1 and not x.is_contiguous():
-            x = x.contiguous()
-        return x
+        return u8_rows(x)
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, bgr: bool = True) -> torch.Tensor:
         """x: uint8 [N,192,192,3] on the GPU (the warped crop; B,G,R order unless ``bgr=False``) -> fc1's output,
         float32 [N,212].  The batch dimension may be strided."""
-        x = self._check_u8(x, IN_SIZE, "Landmark106.forward")
+        x, bs = self._check_u8(x, IN_SIZE, "Landmark106.forward")
         rt = self._runtime(x.device)
         N = x.shape[0]
         pred = torch.empty(N, 2 * N_POINTS, dtype=torch.float32, device=x.device)
         if N == 0:
             return pred
-        ws = self._workspace(rt, N, x.device)
-        bs = x.stride(0) if N > 1 else IN_SIZE * IN_SIZE * 3
+        ws = rt.batch_workspace(N, x.device)
         _lib.check(rt.lib.ghost_lmk_forward(rt.h, x.data_ptr(), bs, 1 if bgr else 0, N, pred.data_ptr(), ws.data_ptr(),
                                             ws.numel(), _lib.stream_ptr(x.device)), "Landmark106.forward")
         return pred
@@ -145,30 +98,25 @@ class Landmark106(PackedModule):
     @torch.no_grad()
     def forward_taps(self, x: torch.Tensor, bgr: bool = True):
         """forward + the stored outputs of conv_2, conv_7, conv_14 and conv_15 as NCHW views in the compute dtype."""
-        x = self._check_u8(x, IN_SIZE, "Landmark106.forward_taps")
+        x, _ = self._check_u8(x, IN_SIZE, "Landmark106.forward_taps")
         rt = self._runtime(x.device)
         N = x.shape[0]
         bufs = [torch.empty(N, s, s, c, dtype=rt.dtype, device=x.device) for _n, c, s in TAPS]
-        ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in bufs])
-        _lib.check(rt.lib.ghost_lmk_set_taps(rt.h, ptrs, 4), "landmark taps")
-        try:
+        with rt.taps([t.data_ptr() for t in bufs], "landmark taps"):
             pred = self.forward(x, bgr)
-        finally:
-            rt.lib.ghost_lmk_set_taps(rt.h, None, 0)
         return pred, [t.permute(0, 3, 1, 2) for t in bufs]
 
     @torch.no_grad()
     def landmarks_u8(self, crops: torch.Tensor, return_pred: bool = False):
         """``get_without_detection_without_transform`` over a batch: uint8 BGR crops [N,224,224,3] on the GPU ->
         float32 [N,106,2] on the GPU, in the crop's pixel coordinates (and fc1's output with ``return_pred``)."""
-        crops = self._check_u8(crops, CROP_SIZE, "Landmark106.landmarks_u8")
+        crops, bs = self._check_u8(crops, CROP_SIZE, "Landmark106.landmarks_u8")
         rt = self._runtime(crops.device)
         N = crops.shape[0]
         lm = torch.empty(N, N_POINTS, 2, dtype=torch.float32, device=crops.device)
         pred = torch.empty(N, 2 * N_POINTS, dtype=torch.float32, device=crops.device) if return_pred else None
         if N:
-            ws = self._workspace(rt, N, crops.device)
-            bs = crops.stride(0) if N > 1 else CROP_SIZE * CROP_SIZE * 3
+            ws = rt.batch_workspace(N, crops.device)
             _lib.check(rt.lib.ghost_lmk_landmarks_u8(rt.h, crops.data_ptr(), bs, N, lm.data_ptr(), _lib.ptr(pred),
                                                      ws.data_ptr(), ws.numel(), _lib.stream_ptr(crops.device)),
                        "Landmark106.landmarks_u8")

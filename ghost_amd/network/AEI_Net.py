@@ -23,6 +23,7 @@ bf16 storage.  There is no CPU path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -30,7 +31,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .._packed import PackedModule, WorkspaceCache
+from .._packed import NativeRuntime, PackedModule
 from .AADLayer import AAD_ResBlk, AADLayer, AddBlocksSequential  # noqa: F401  (reference re-exports)
 from .pack import pack_all
 from .resnet import MLAttrEncoderResnet
@@ -133,24 +134,14 @@ class AADGenerator(nn.Module):
 OPTIONS = {"fuse_upsample": 0, "fuse_stats": 1, "two_streams": 2, "tap_partials": 3, "fuse_reduce": 4}
 
 
-class _Runtime:
+class _Runtime(NativeRuntime):
     """Native handle + packed weights for one (device, compute dtype)."""
 
     def __init__(self, backbone, num_blocks, c_id, dtype, slots, options=None):
-        self.lib = _lib.load()
-        self.dtype = dtype
-        h = C.c_void_p()
-        _lib.check(self.lib.ghost_aei_create(backbone.encode(), num_blocks, c_id, _lib.gdtype(dtype), C.byref(h)),
-                   "ghost_aei_create")
-        self.h = h
-        self.slots = slots  # keeps the packed tensors alive
-        for name, t in slots.items():
-            _lib.check(self.lib.ghost_aei_bind(h, name.encode(), t.data_ptr(), t.numel()), f"bind {name}")
-        if self.lib.ghost_aei_missing(h) != 0:
-            _lib.check(-2, "weights incomplete")
+        super().__init__("aei", "", dtype, slots, backbone.encode(), num_blocks, c_id, _lib.gdtype(dtype))
+        h = self.h
         for name, v in (options or {}).items():
             _lib.check(self.lib.ghost_aei_set_option(h, OPTIONS[name], int(v)), f"option {name}")
-        self.ws = WorkspaceCache()   # (mode, B, stream) -> workspace (stream-ordered reuse)
         self.geom = []
         for k in range(1, 9):
             c_, h_, w_ = C.c_int(), C.c_int(), C.c_int()
@@ -158,22 +149,13 @@ class _Runtime:
             self.geom.append((c_.value, h_.value, w_.value))
 
     def workspace(self, mode: str, B: int, dev: torch.device, stream: int) -> torch.Tensor:
+        """One workspace per (mode, B, stream): stream-ordered reuse."""
         fn = {"swap": self.lib.ghost_aei_swap_workspace_bytes,
               "idtable": self.lib.ghost_aei_identity_table_workspace_bytes}.get(mode, self.lib.ghost_aei_workspace_bytes)
+        return self.workspace_for(lambda: fn(self.h, B), (mode, B, stream), dev)
 
-        def nbytes():
-            n = fn(self.h, B)
-            if n < 0:
-                _lib.check(int(n), "workspace sizing")
-            return n
-        return self.ws.get((mode, B, stream), nbytes, dev)
-
-    def __del__(self):
-        try:
-            if self.h:
-                self.lib.ghost_aei_destroy(self.h)
-        except Exception:
-            pass
+    def _set_taps(self, ptrs):   # eight pointers, or null to clear: this ABI takes no count
+        return self.lib.ghost_aei_set_taps(self.h, (C.c_void_p * 8)(*ptrs) if ptrs else None)
 
 
 class IdentityTable:
@@ -300,15 +282,11 @@ class AEI_Net(PackedModule):
         if taps:
             cin_cout = [(1024, 1024), (1024, 1024), (1024, 1024), (1024, 512), (512, 256), (256, 128), (128, 64)]
             blocks = [torch.empty(B, 2 ** k, 2 ** k, cin_cout[k - 1][1], dtype=rt.dtype, device=dev) for k in range(1, 8)]
-            _lib.check(lib.ghost_aei_set_taps(rt.h, (C.c_void_p * 8)(*[b.data_ptr() for b in blocks], None)), "taps")
-        try:
+        with rt.taps([b.data_ptr() for b in blocks] + [None], "taps") if taps else contextlib.nullcontext():
             _lib.check(lib.ghost_aei_forward(rt.h, Xt.data_ptr(), _lib.gdtype(Xt.dtype), st, B, z.data_ptr(),
                                              _lib.gdtype(z.dtype), z.stride(0), Y.data_ptr(),
                                              out_u8.data_ptr() if out_u8 is not None else None, ap, ws.data_ptr(),
                                              ws.numel(), stream), "AEI_Net.forward")
-        finally:
-            if taps:
-                lib.ghost_aei_set_taps(rt.h, None)
         od = self._out_dtype(rt)
         Y = Y.permute(0, 3, 1, 2)
         attrs = tuple(a.permute(0, 3, 1, 2) for a in attrs)
