@@ -251,8 +251,13 @@ struct BlurArgs {
 
 constexpr int kMaxTaps = 256;
 
-// cv2.getGaussianKernel(n, sigma) normalised in double, stored as float; n = cvRound(6 sigma + 1) | 1
+// cv2.getGaussianKernel(n, sigma) normalised in double, stored as float; n = cvRound(6 sigma + 1) | 1.
+// 0 taps for a sigma outside 1..42: sigma < 1 has no kernel (sigma 0 would give exp(-inf * 0) = NaN taps, and cv2
+// raises for it), sigma >= 43 needs more than kMaxTaps.  Either pass with 0 taps sums nothing, so a frame with such
+// a sigmaX or sigmaY gets an all-zero mask, never NaN (the paste-back then leaves the frame untouched); the Python
+// wrappers that take host parameters refuse such a sigma before the launch.
 __device__ int gauss_taps(int sigma, float* k) {
+  if (sigma < 1) return 0;
   const double s = (double)sigma, sc = -0.5 / (s * s);
   const int n = ((int)floor(s * 6.0 + 1.0 + 0.5)) | 1;
   if (n > kMaxTaps) return 0;
@@ -362,6 +367,10 @@ extern "C" int ghost_mask_polygons(const float* landmarks, int F, int npts, cons
   return 0;
 }
 
+// Workspace layout, a test-support contract (tests/test_mask_raster_gpu.py reads the stages from it): when
+// ghost_face_masks has returned and its stream has drained, the first F*H*W bytes hold the uint8 masks [F][H][W] after
+// the raster, the erode / dilate and the border fade, and the fp32 planes [F][H][W] of the blur's row pass start at
+// the next 256-byte boundary (of the address) after them.
 extern "C" int64_t ghost_face_masks_workspace_bytes(int F, int H, int W) {
   return (int64_t)F * H * W * (1 + 4) + 256;
 }

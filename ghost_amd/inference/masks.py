@@ -57,14 +57,36 @@ def mask_polygons(landmarks: np.ndarray, params: np.ndarray):
     return poly, nv
 
 
+MAX_SIGMA = 42   # 6 sigma + 1 = 253 taps, the most the blur kernel holds (masks.hip kMaxTaps = 256)
+MAX_ERODE = 256  # a larger box than the tallest image (masks.hip kMaxRows) erases or fills every mask
+
+
+def check_params(params) -> np.ndarray:
+    """params as int32 [F,3] (erode, sigmaX, sigmaY), or ValueError: a sigma outside 1..42 has no blur on the device
+    (cv2 raises for sigma 0; the kernel has no room for the taps of sigma >= 43 and would return an all-zero mask)
+    and |erode| > 256 is no face mask.  Host data only: nothing here touches the device."""
+    pr = np.asarray(params, dtype=np.int32).reshape(-1, 3)
+    bad = (pr[:, 1:] < 1) | (pr[:, 1:] > MAX_SIGMA)
+    if bad.any():
+        f = int(np.flatnonzero(bad.any(axis=1))[0])
+        raise ValueError(f"ghost_amd: face mask sigmaX / sigmaY must be in 1..{MAX_SIGMA}, got params "
+                         f"{pr[f].tolist()} for frame {f}")
+    if (np.abs(pr[:, 0].astype(np.int64)) > MAX_ERODE).any():
+        f = int(np.flatnonzero(np.abs(pr[:, 0].astype(np.int64)) > MAX_ERODE)[0])
+        raise ValueError(f"ghost_amd: face mask |erode| must be at most {MAX_ERODE}, got params {pr[f].tolist()} "
+                         f"for frame {f}")
+    return pr
+
+
 def face_masks(landmarks, params, H: int = 224, W: int = 224, device=None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Masks of F frames: landmarks [F,106,2] (the swap's, as the landmark model returns them), params [F,3]
-    (erode, sigmaX, sigmaY) -> float32 [F,H,W] on ``device`` (face_mask_static's mask / 255 per frame)."""
+    (erode, sigmaX, sigmaY) -> float32 [F,H,W] on ``device`` (face_mask_static's mask / 255 per frame).
+    ValueError, before anything touches the device, for a sigma outside 1..42 or |erode| > 256 (``check_params``)."""
+    pr = check_params(params)
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if dev.type != "cuda":
         raise RuntimeError("ghost_amd: face_masks runs on the GPU only (no CPU path)")
-    pr = np.asarray(params, dtype=np.int32).reshape(-1, 3)
     poly, nv = mask_polygons(landmarks, pr)
     F = poly.shape[0]
     if F == 0:
@@ -101,7 +123,8 @@ def mask_polygons_device(landmarks: torch.Tensor, params: Optional[torch.Tensor]
 
     Either ``params`` (int32 [F,3], returned as they are) or both reference sets: face f's parameters are
     ``mask_params(landmarks_ref[ref_index[f]], landmarks_tgt[tgt_index[f]])`` (float32 [*,106,2] sets, int32 [F]
-    indices; an index outside its set gives params 0, 0, 0)."""
+    indices; an index outside its set gives params 0, 0, 0).  ``ghost_face_masks`` gives a frame whose sigmaX or
+    sigmaY is outside 1..42, such params included, an all-zero mask (never NaN): the paste-back leaves it untouched."""
     _lib.require_gpu(landmarks, "mask_polygons_device")
     dev = landmarks.device
     lm = _dev_arg(landmarks, torch.float32, (None, 106, 2), dev, "landmarks")

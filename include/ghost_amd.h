@@ -477,7 +477,8 @@ int ghost_roi_unpack_u8(uint8_t* patches, int64_t patch_stride, int Np, int Ph, 
 int ghost_mask_polygons(const float* landmarks, int F, int npts, const int32_t* params, int32_t* poly, int32_t* nv);
 /* Device: poly / nv / params as above (device copies) -> masks [F][H][W] f32 (frame f at f*mask_stride floats):
  * cv2.fillConvexPoly(255), cv2.erode / dilate with the k x k box, the 2*sigmaY border fade, cv2.GaussianBlur
- * (0, 0, sigmaX, sigmaY), / 255.  H*W <= 57344, H <= 256; ws >= ghost_face_masks_workspace_bytes(F, H, W). */
+ * (0, 0, sigmaX, sigmaY), / 255.  H*W <= 57344, H <= 256; ws >= ghost_face_masks_workspace_bytes(F, H, W).
+ * A frame whose sigmaX or sigmaY is outside 1..42 (the blur holds 253 taps at the most) gets an all-zero mask. */
 int64_t ghost_face_masks_workspace_bytes(int F, int H, int W);
 int ghost_face_masks(const int32_t* poly, const int32_t* nv, const int32_t* params, int F, int H, int W, float* masks,
                      int64_t mask_stride, void* ws, int64_t ws_bytes, void* stream);

@@ -90,13 +90,15 @@ def _tdiv(a: int, b: int) -> int:
     return q if (a >= 0) == (b >= 0) else -q
 
 
+def outcode(W: int, H: int, x: int, y: int) -> int:
+    """clipLine's code of a point: 1 left of the image, 2 right of it, 4 above, 8 below."""
+    return (x < 0) + (x > W - 1) * 2 + (y < 0) * 4 + (y > H - 1) * 8
+
+
 def clip_line(W: int, H: int, x1: int, y1: int, x2: int, y2: int):
     """OpenCV clipLine (drawing.cpp) on integer endpoints; returns (inside, x1, y1, x2, y2)."""
     right, bottom = W - 1, H - 1
-
-    def code(x, y):
-        return (x < 0) + (x > right) * 2 + (y < 0) * 4 + (y > bottom) * 8
-    c1, c2 = code(x1, y1), code(x2, y2)
+    c1, c2 = outcode(W, H, x1, y1), outcode(W, H, x2, y2)
     if (c1 & c2) == 0 and (c1 | c2) != 0:
         if c1 & 12:
             a = 0 if c1 < 8 else bottom
@@ -252,7 +254,9 @@ def _reflect101(i: np.ndarray, n: int) -> np.ndarray:
     return np.where(i >= n, p - i, i)
 
 
-def gaussian_blur(mask: np.ndarray, sx: float, sy: float) -> np.ndarray:
+def gaussian_blur_planes(mask: np.ndarray, sx: float, sy: float):
+    """The two fp32 planes of the separable filter before any rounding: (after the row pass, after the column pass);
+    each tap's product rounded to fp32, then added in tap order."""
     H, W = mask.shape
     kx, ky = gaussian_kernel(sx), gaussian_kernel(sy)
     m = mask.astype(np.float32)
@@ -265,7 +269,16 @@ def gaussian_blur(mask: np.ndarray, sx: float, sy: float) -> np.ndarray:
     out = np.zeros((H, W), dtype=np.float32)
     for t in range(len(ky)):
         out = out + ky[t] * tmp[rows[:, t], :]
-    return np.clip(np.rint(out), 0, 255).astype(np.uint8)
+    return tmp, out
+
+
+def round_u8(plane: np.ndarray) -> np.ndarray:
+    """cvRound (half to even) and saturate_cast<uchar>."""
+    return np.clip(np.rint(plane), 0, 255).astype(np.uint8)
+
+
+def gaussian_blur(mask: np.ndarray, sx: float, sy: float) -> np.ndarray:
+    return round_u8(gaussian_blur_planes(mask, sx, sy)[1])
 
 
 def face_mask_static(H: int, W: int, landmarks: np.ndarray, landmarks_tgt=None, params=None):
